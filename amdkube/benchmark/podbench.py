@@ -200,16 +200,21 @@ class PodBench:
         if rec.get("cpu"):
             if ph == "Running" and "started" in rec and "done" not in rec:
                 rec["done"] = now
+                rec["phase"] = ph
                 ev = self.done_events.get(name)
                 if ev:
                     ev.set()
             elif ph == "Failed" and "done" not in rec:
                 rec["done"] = now
+                rec["phase"] = ph
                 self.failed.append(f"{name}: {st.get('reason')} {st.get('message')}")
                 self.done_events[name].set()
             return
         if ph in ("Succeeded", "Failed") and "done" not in rec:
             rec["done"] = now
+            rec["phase"] = ph
+            rec["exit_codes"] = [((cs.get("state") or {}).get("terminated") or {}).get("exitCode")
+                                 for cs in st.get("containerStatuses") or []]
             rec.setdefault("started", now)
             rec.setdefault("bound", now)
             if ph == "Failed":
@@ -288,8 +293,10 @@ class PodBench:
         t0 = time.perf_counter()
         self.step_devices = []
         names = []
+        last = []
         for _ in range(steps):
-            names += await (self.density_step() if self.mode == "density" else self.step())
+            last = await (self.density_step() if self.mode == "density" else self.step())
+            names += last
         el = time.perf_counter() - t0
         cpu_recs = [self.t[n] for n in names if self.t[n].get("cpu")]
         names_all = names
@@ -313,7 +320,20 @@ class PodBench:
                 "p99_node_startup_ms": ms(pct(node, 99)), "p50_schedule_ms": ms(pct(sched, 50)),
                 "p50_pod_runtime_ms": ms(pct(life, 50)),
                 "gpu_devices_per_step": [len(d) for d in self.step_devices],
-                "gpu_devices_seen": sorted({d for ds in self.step_devices for d in ds})}
+                "gpu_devices_seen": sorted({d for ds in self.step_devices for d in ds}),
+                "last_step": self._outcomes(last)}
+
+    def _outcomes(self, names: list[str]) -> dict:
+        """What the last step's pods came to, in creation order (bench.py --dump-outputs): per pod
+        whether it is a GPU pod and whether it reached its goal (pause pod Running, GPU pod
+        Succeeded); per GPU pod its container's exit code and the number of GPUs it was assigned."""
+        recs = [self.t[n] for n in names]
+        gpu = [r for r in recs if not r.get("cpu")]
+        code = lambda r: next((c for c in r.get("exit_codes") or [] if c is not None), -1)  # noqa: E731
+        return {"pod_is_gpu": [0 if r.get("cpu") else 1 for r in recs],
+                "pod_reached_goal": [int(r.get("phase") == ("Running" if r.get("cpu") else "Succeeded")) for r in recs],
+                "gpu_pod_exit_code": [code(r) for r in gpu],
+                "gpu_pod_devices_assigned": [len(r.get("devices") or []) for r in gpu]}
 
     # ------------------------------------------------------------ node density (density_test.go)
     async def _create_and_wait(self, names: list[str], gpu: set, interval: float = 0.0, timeout: float = 300.0):

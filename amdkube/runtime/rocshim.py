@@ -339,6 +339,16 @@ def _prepare_sandbox_fs(log_dir: str, rootfs: str, resolv: str | None):
             f.write(resolv)
 
 
+def _mount_point_possible(path: str) -> bool:
+    """The path exists, or this user may create it under its nearest existing directory."""
+    if os.path.lexists(path):
+        return True
+    parent = os.path.dirname(path.rstrip("/")) or "/"
+    while not os.path.lexists(parent):
+        parent = os.path.dirname(parent) or "/"
+    return os.path.isdir(parent) and os.access(parent, os.W_OK | os.X_OK)
+
+
 def _prepare_container_fs(root: str, log_dir: str, links: list[tuple[str, str]]):
     """A container's directories and volume links (run in a worker thread: directory creation
     costs ~0.2 ms a call on a journaled filesystem, several per container)."""
@@ -949,6 +959,11 @@ class RocShim:
             a += ["--apparmor", aa]
         for mnt in c.mounts:   # volumes and the pod's resolv.conf in the private mount namespace
             if mnt["container_path"].startswith("/") and os.path.exists(mnt["host_path"]):
+                if self.isolation == "userns" and not c.resources.get("rootfs") and not _mount_point_possible(mnt["container_path"]):
+                    # a container on the node's own root, run by an unprivileged user: a mount point this
+                    # user may not create (/dev/termination-log) is left out, as it is without a mount namespace
+                    log.info("container %s: no mount point %s for this user, volume not mounted", c.name, mnt["container_path"])
+                    continue
                 a += ["--bind", f"{mnt['host_path']}:{mnt['container_path']}" + (":ro" if mnt.get("readonly") else "")]
         if c.resources.get("rootfs") and c.handler == "rocm":
             # the rocm handler's injection (the nvidia runtime's driver-library hook, re-homed):

@@ -1,7 +1,7 @@
 """amdkube headline benchmark: pod density throughput + p50 GPU-pod startup latency on one
 MI355X node with N allocatable GPUs (BASELINE.json metric; SURVEY §6 mapping).
 
-  python bench.py [--gpus N] [--steps K] [--warmup W] [--mode density|churn]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--mode density|churn] [--dump-outputs DIR] [--full]
   torchrun --nproc-per-node N bench.py --gpus N ...   (one rank per GPU; rank 0 drives)
 
 Rank 0 launches the node (apiserver, scheduler, rocshim, AMD device plugin on amd-smi,
@@ -19,7 +19,11 @@ percentiles are reported beside it. churn — GPU pods only, P per GPU per step 
 process-lifetime bound; docs/PERFORMANCE.md).
 
 Baselines: density saturation ≥ 8 pods/s (vs_baseline = value / 8),
-pod startup p50/p90/p99 ≤ 5 s, scheduler throughput ≥ 30 pods/s (goal 100). Extra fields,
+pod startup p50/p90/p99 ≤ 5 s, scheduler throughput ≥ 30 pods/s (goal 100).
+
+A plain run sets up the node, warms up, times the K steps, writes the last step's pod outcomes
+if --dump-outputs is given (per pod: GPU pod or not, goal reached; per GPU pod: exit code, GPUs
+assigned) and prints the result line. Extra fields, only with --full and
 all measured after the timed region: the node-density tests of test/e2e_node/density_test.go
 (batch of 10, 10 in sequence beside 50 background pods) with the kubelet's and runtime's CPU
 cores p50/p95 and RSS and the API call p99, each beside its reference limit
@@ -41,6 +45,17 @@ BASELINE_PODS_PER_S = 8.0      # test/e2e/scalability/density.go:55-56 MinPodsPe
 SLO_STARTUP_MS = 5000.0        # test/e2e/framework/metrics_util.go:46
 
 
+def dump_outputs(path, last_step):
+    """What the timed path handed back for its last step, one float32 array per name. The step's
+    inputs are fixed by the arguments (N GPU pods adding the same 50,000 seeded fp32 elements,
+    the density share of pause pods), so two builds run with the same arguments compare array
+    for array; timings are left out."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    for name, values in last_step.items():
+        np.save(os.path.join(path, name + ".npy"), np.asarray(values, dtype=np.float32))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=None)
@@ -50,10 +65,15 @@ def main():
     ap.add_argument("--mode", default="density", choices=("density", "churn"),
                     help="density: the reference density.go mix on the real node (default); churn: GPU pods only")
     ap.add_argument("--backend", default="auto", help="amdsmi|sysfs|fake|auto")
-    ap.add_argument("--no-sched-perf", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run the node-density tests, scheduler_perf and the hollow-node "
+                         "density run (each can be dropped with the three options below)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step's pods came to as DIR/<name>.npy (float32)")
+    ap.add_argument("--no-sched-perf", action="store_true", help="with --full: skip scheduler_perf")
     ap.add_argument("--no-node-density", action="store_true",
-                    help="skip the density_test.go batch/sequence tests with resource sampling (after the timed region)")
-    ap.add_argument("--density-nodes", type=int, default=100, help="hollow-node density run (0 = skip)")
+                    help="with --full: skip the density_test.go batch/sequence tests with resource sampling")
+    ap.add_argument("--density-nodes", type=int, default=100, help="with --full: hollow-node density run (0 = skip)")
     ap.add_argument("--image", default="rocm/vector-add", help="GPU pod image (CPU rehearsals: busybox)")
     ap.add_argument("--pod-arg", action="append", default=[], help="GPU pod container argument (repeatable)")
     ap.add_argument("--isolation", default=None, help="rocshim device isolation (default: auto on real GPUs)")
@@ -121,18 +141,20 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         el = float(t.item())
     if rank == 0:
+        if a.dump_outputs:
+            dump_outputs(a.dump_outputs, res["last_step"])
         node_density = None
-        if not a.no_node_density:
+        if a.full and not a.no_node_density:
             worker.stdin.write(json.dumps({"cmd": "node_density"}) + "\n")
             worker.stdin.flush()
             node_density = json.loads(worker.stdout.readline())
         sched = None
-        if not a.no_sched_perf:
+        if a.full and not a.no_sched_perf:
             worker.stdin.write(json.dumps({"cmd": "schedperf", "nodes": 100, "pods": 3000}) + "\n")
             worker.stdin.flush()
             sched = json.loads(worker.stdout.readline())
         density = None
-        if a.density_nodes:
+        if a.full and a.density_nodes:
             # the reference's headline density test (30 pods/node saturation) on hollow MI355X nodes;
             # a child process so its control plane does not share this rank's core (not timed)
             env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT")}

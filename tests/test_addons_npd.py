@@ -148,23 +148,23 @@ def test_multiline_pattern_matches_only_at_the_newest_entry():
     assert not mon.process(LogEntry(t, "something else")).events       # an old match does not re-fire
 
 
-def test_kernel_log_gpu_fault_takes_the_gpu_out_of_service(tmp_path):
+def test_kernel_log_gpu_fault_takes_the_gpu_out_of_service(short_tmp):
     """npd amdgpu rule (kmsg) → <health-state>.faults → the device plugin marks exactly that GPU
     Unhealthy with the kernel's words, sticky across a plugin restart; the node gets the
     AMDGPUProblem condition."""
     from amdkube.deviceplugin.amd import AMDGPUPlugin
     from amdkube.smi import FakeBackend, device_id
     from amdkube.smi.health import HEALTH_REASON_ATTR
-    state = str(tmp_path / "dp" / "health.json")
+    state = str(short_tmp / "dp" / "health.json")
     fb = FakeBackend(n=2)
     bdf1 = fb.gpus()[1]["bdf"]
     boot = time.time() - 50
-    cfg = _amdgpu_monitor(tmp_path, [f"amdgpu {bdf1}: amdgpu: poison is consumed by client 12, kick off gpu reset flow"], boot)
+    cfg = _amdgpu_monitor(short_tmp, [f"amdgpu {bdf1}: amdgpu: poison is consumed by client 12, kick off gpu reset flow"], boot)
 
     async def go():
         async with LocalCluster(gpus="none", with_kubelet=False, with_controllers=False) as lc:
             await lc.client.create({"apiVersion": "v1", "kind": "Node", "metadata": {"name": "gpu-node"}})
-            p = AMDGPUPlugin(fb, plugins_dir=str(tmp_path / "dp" / "plugins"), health_interval=0.05, health_state=state)
+            p = AMDGPUPlugin(fb, plugins_dir=str(short_tmp / "dp" / "plugins"), health_interval=0.05, health_state=state)
             await p.start()
             npd = NodeProblemDetector(lc.client, "gpu-node", [cfg], health_state=state, boot=boot, poll=0.05)
             await npd.start()
@@ -183,7 +183,7 @@ def test_kernel_log_gpu_fault_takes_the_gpu_out_of_service(tmp_path):
             assert cond["XGMILinkProblem"]["status"] == "False"
             await npd.stop()
             await p.stop()
-            p2 = AMDGPUPlugin(fb, plugins_dir=str(tmp_path / "dp" / "plugins"), health_interval=0.05, health_state=state)
+            p2 = AMDGPUPlugin(fb, plugins_dir=str(short_tmp / "dp" / "plugins"), health_interval=0.05, health_state=state)
             await p2.start()
             h = {d["ID"]: d["health"] for d in p2.devices}
             assert h == {ids[0]: "Healthy", ids[1]: "Unhealthy"}

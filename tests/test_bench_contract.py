@@ -16,8 +16,13 @@ def _port():
         return s.getsockname()[1]
 
 
+# the gloo rehearsals hide the node's GPUs from their ranks: with a GPU visible bench.py takes nccl,
+# which refuses several ranks on one device
+NO_GPU = {"HIP_VISIBLE_DEVICES": "-1", "CUDA_VISIBLE_DEVICES": "-1"}
+
+
 def test_bench_two_ranks_gloo():
-    env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0", AMDKUBE_REQUIRE_NATIVE="0")
+    env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0", AMDKUBE_REQUIRE_NATIVE="0", **NO_GPU)
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr",
            "127.0.0.1", "--master-port", str(_port()), "bench.py", "--gpus", "2", "--steps", "2", "--warmup", "1",
            "--backend", "fake", "--no-sched-perf", "--density-nodes", "0", "--image", "busybox",
@@ -38,7 +43,7 @@ def test_bench_eight_ranks_gloo_fake_8gpu_node():
     """The driver's N=8 launch rehearsed on CPU: torchrun --nproc-per-node 8 over gloo, a fake
     8×MI355X node, busybox GPU pods. One JSON line, n_gpus 8, every step's 8 GPU pods on 8
     distinct device IDs, and the timed region MAX-reduced over the 8 ranks."""
-    env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0", AMDKUBE_REQUIRE_NATIVE="0", OMP_NUM_THREADS="1")
+    env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0", AMDKUBE_REQUIRE_NATIVE="0", OMP_NUM_THREADS="1", **NO_GPU)
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "8", "--master-addr",
            "127.0.0.1", "--master-port", str(_port()), "bench.py", "--gpus", "8", "--steps", "2", "--warmup", "1",
            "--backend", "fake", "--no-sched-perf", "--no-node-density", "--density-nodes", "0", "--image", "busybox",
@@ -55,11 +60,35 @@ def test_bench_eight_ranks_gloo_fake_8gpu_node():
     assert d["config"]["parallelism"] == "8 allocatable MI355X"
 
 
+def test_bench_plain_run_times_its_steps_and_dumps_the_last_one(tmp_path):
+    """Without --full nothing but the timed steps is measured; --steps sets how many there are, and
+    --dump-outputs writes the last step's pod outcomes as float32 arrays."""
+    import numpy as np
+    env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0", AMDKUBE_REQUIRE_NATIVE="0")
+    cmd = [sys.executable, "bench.py", "--gpus", "2", "--steps", "3", "--warmup", "1", "--backend", "fake",
+           "--image", "busybox", "--pod-arg=-c", "--pod-arg=true", "--dump-outputs", str(tmp_path / "out")]
+    r = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=240)
+    assert r.returncode == 0, r.stderr[-3000:]
+    lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
+    assert len(lines) == 1, r.stdout
+    d = json.loads(lines[0])
+    assert d["steps"] == 3 and d["gpu_pods"] == 3 * 2 and d["gpu_devices_per_step"] == [2, 2, 2] and d["failed_pods"] == 0, d
+    assert d["ms_per_step"] > 0 and d["dtype"] == "fp32" and d["unit"] == "pods/s" and d["higher_is_better"] is True
+    assert d["sched_perf"] is None and d["density"] is None and "node_density" not in d
+    got = {p.name: np.load(p) for p in (tmp_path / "out").iterdir()}
+    assert sorted(got) == ["gpu_pod_devices_assigned.npy", "gpu_pod_exit_code.npy", "pod_is_gpu.npy", "pod_reached_goal.npy"]
+    assert all(v.dtype == np.float32 for v in got.values())
+    n_cpu = round(22 * 2 / 8)
+    assert got["pod_is_gpu.npy"].tolist() == [1.0] * 2 + [0.0] * n_cpu
+    assert got["pod_reached_goal.npy"].tolist() == [1.0] * (2 + n_cpu)
+    assert got["gpu_pod_exit_code.npy"].tolist() == [0.0, 0.0] and got["gpu_pod_devices_assigned.npy"].tolist() == [1.0, 1.0]
+
+
 def test_bench_node_density_fields_single_rank():
     """The density_test.go fields (batch of 10, 10-in-sequence with 50 background, kubelet and
     runtime CPU/RSS, API p99) are reported beside their limits."""
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0", AMDKUBE_REQUIRE_NATIVE="0")
-    cmd = [sys.executable, "bench.py", "--gpus", "2", "--steps", "1", "--warmup", "0", "--backend", "fake",
+    cmd = [sys.executable, "bench.py", "--gpus", "2", "--steps", "1", "--warmup", "0", "--backend", "fake", "--full",
            "--no-sched-perf", "--density-nodes", "0", "--image", "busybox", "--pod-arg=-c", "--pod-arg=true"]
     r = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=300)
     assert r.returncode == 0, r.stderr[-3000:]

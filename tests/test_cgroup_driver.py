@@ -292,7 +292,7 @@ async def _wait_exit(shim, cid):
     raise AssertionError("container did not exit")
 
 
-@pytest.mark.skipif(os.geteuid() != 0, reason="namespaces isolation needs root")
+@pytest.mark.needs_root          # namespaces isolation
 def test_rocshim_places_containers_in_systemd_scopes(tmp_path):
     from amdkube.runtime import RocShim
     from amdkube.kubelet.qos import cgroup_parent

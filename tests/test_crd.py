@@ -107,6 +107,7 @@ async def test_custom_resources_served_validated_and_finalized():
 def test_kubectl_discovers_custom_resources(tmp_path, capsys):
     """kubectl in its own process knows only built-in kinds: a custom resource name is resolved
     through the server's discovery documents."""
+    import os
     import subprocess
     import sys
 
@@ -119,7 +120,8 @@ def test_kubectl_discovers_custom_resources(tmp_path, capsys):
                 await asyncio.sleep(0.05)
             f = tmp_path / "job.yaml"
             f.write_text("apiVersion: amd.com/v1alpha1\nkind: GPUJob\nmetadata:\n  name: train\nspec:\n  gpus: 4\n  image: rocm/pytorch\n")
-            env = {"PYTHONPATH": "/root/repo", "PATH": "/usr/bin:/bin", "AMDKUBE_SERVER": lc.api.url}
+            root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+            env = {"PYTHONPATH": root, "PATH": "/usr/bin:/bin", "AMDKUBE_SERVER": lc.api.url}
             tok = ["--token", lc.api.loopback_token]
             run = lambda *args: asyncio.get_running_loop().run_in_executor(None, lambda: subprocess.run(
                 [sys.executable, "-m", "amdkube", "kubectl", *tok, *args], capture_output=True, text=True, env=env, timeout=60))

@@ -96,7 +96,7 @@ def test_fault_flips_device_publishes_reason_and_spares_the_running_pod():
     run(go(), 90)
 
 
-def test_fault_survives_a_plugin_restart_until_an_operator_reset(tmp_path):
+def test_fault_survives_a_plugin_restart_until_an_operator_reset(short_tmp):
     """Round-3 review: the baseline and sticky faults lived only in memory, so a restarted plugin
     re-baselined and re-advertised a faulted GPU Healthy. With the checkpoint the restarted
     plugin keeps the GPU Unhealthy with its reason, and judges against the ORIGINAL baseline
@@ -105,11 +105,11 @@ def test_fault_survives_a_plugin_restart_until_an_operator_reset(tmp_path):
     import sys
     from amdkube.deviceplugin.amd import AMDGPUPlugin
     from amdkube.smi import device_id
-    state = str(tmp_path / "health.json")
+    state = str(short_tmp / "health.json")
     fb = FakeBackend(n=2)
 
     async def plugin():
-        p = AMDGPUPlugin(fb, plugins_dir=str(tmp_path / "plugins"), health_interval=0.05, health_state=state)
+        p = AMDGPUPlugin(fb, plugins_dir=str(short_tmp / "plugins"), health_interval=0.05, health_state=state)
         await p.start()
         return p
 

@@ -246,7 +246,7 @@ def test_image_config_precedence_and_gc_through_cri(tmp_path):
     run(go())
 
 
-@pytest.mark.skipif(os.geteuid() != 0, reason="pivot_root into an overlay needs root (or a user namespace)")
+@pytest.mark.needs_root          # pivot_root into an overlay needs root (or a user namespace)
 def test_nsexec_pivots_into_the_image(tmp_path):
     arch = tmp_path / "img.tar"
     layer = host_closure("/bin/sh", "/bin/cat", "/bin/ls") + [("etc", None, 0o755, None), ("etc/marker", b"in-image", 0o644, None)]

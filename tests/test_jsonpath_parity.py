@@ -87,7 +87,8 @@ def test_parser_malformed_input():
     ("{*}", "unrecognized character in action: U+002A '*'"),
     ("{+12.3.0}", "cannot parse number +12.3.0"),
     ("{[1}", "unterminated array"),
-    ("{[::-1]}", "invalid array index ::-1"),
+    # an id of its own: the generated one would hold "::", which separates the parts of a test id
+    pytest.param("{[::-1]}", "invalid array index ::-1", id="negative-step"),
     ("{[?(.price]}", "unterminated filter"),
 ])
 def test_fail_parser(text, err):

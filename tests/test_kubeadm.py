@@ -43,8 +43,8 @@ def test_token_format_and_ca_pin(tmp_path):
 
 
 @pytest.mark.slow
-def test_kubeadm_init_join_reset(tmp_path):
-    master, worker = str(tmp_path / "master"), str(tmp_path / "worker")
+def test_kubeadm_init_join_reset(short_tmp):
+    master, worker = str(short_tmp / "master"), str(short_tmp / "worker")
     port = _free_port()
     try:
         r = _kubeadm("init", "--base-dir", master, "--apiserver-bind-port", str(port), "--node-name", "master-0",
@@ -57,7 +57,7 @@ def test_kubeadm_init_join_reset(tmp_path):
         server, token, h = join.groups()
         # a wrong CA pin is refused
         bad = _kubeadm("join", server, "--token", token, "--discovery-token-ca-cert-hash", "sha256:" + "0" * 64,
-                       "--base-dir", str(tmp_path / "bad"), "--node-name", "bad", "--timeout", "20")
+                       "--base-dir", str(short_tmp / "bad"), "--node-name", "bad", "--timeout", "20")
         assert bad.returncode != 0 and "does not match" in bad.stderr
         r = _kubeadm("join", server, "--token", token, "--discovery-token-ca-cert-hash", h, "--base-dir", worker,
                      "--node-name", "worker-1", "--start-kubelet", "--kubelet-port", "0")
@@ -76,7 +76,7 @@ def test_kubeadm_init_join_reset(tmp_path):
         assert r.returncode == 0 and "kube-scheduler" in r.stdout and "up-to-date" in r.stdout, r.stdout + r.stderr
         r = _kubeadm("upgrade", "apply", "v1.8.0", "--kubeconfig", admin, "--base-dir", master, "-y")
         assert r.returncode == 1 and "lower than the minor release" in r.stderr
-        newcfg = tmp_path / "upgrade.yaml"
+        newcfg = short_tmp / "upgrade.yaml"
         newcfg.write_text("apiVersion: kubeadm.k8s.io/v1alpha1\nkind: MasterConfiguration\n"
                           "schedulerExtraArgs: {kube-api-qps: '400'}\n")
         r = _kubeadm("upgrade", "apply", "--kubeconfig", admin, "--base-dir", master, "--config", str(newcfg), "-y",
@@ -145,13 +145,13 @@ async def _check_cluster(admin_conf):
         await c.close()
 
 
-def test_kubeadm_local_etcd_static_pod(tmp_path):
+def test_kubeadm_local_etcd_static_pod(short_tmp):
     """etcd.dataDir in the MasterConfiguration: kubeadm writes an `amdkube etcd` static Pod
     (app/phases/etcd/local.go), the apiserver stores through --etcd-servers, the objects land
     in etcd's data directory, and reset removes that directory (reset.go resetEtcd)."""
-    base, etcd_dir = str(tmp_path / "master"), str(tmp_path / "etcd-data")
+    base, etcd_dir = str(short_tmp / "master"), str(short_tmp / "etcd-data")
     port, eport = _free_port(), _free_port()
-    cfg = tmp_path / "cfg.yaml"
+    cfg = short_tmp / "cfg.yaml"
     cfg.write_text("apiVersion: kubeadm.k8s.io/v1alpha1\nkind: MasterConfiguration\n"
                    f"etcd:\n  dataDir: {etcd_dir}\n  extraArgs:\n    listen-client-urls: http://127.0.0.1:{eport}\n")
     try:
@@ -210,14 +210,14 @@ def test_kubeadm_store_modes():
     assert e[e.index("--snapshot-count") + 1] == "10000"
 
 
-def test_kubeadm_self_hosting(tmp_path):
+def test_kubeadm_self_hosting(short_tmp):
     """--feature-gates SelfHosting=true,StoreCertsInSecrets=true: the static control plane
     becomes DaemonSets self-hosted-kube-{apiserver,controller-manager,scheduler}
     (selfhosting.go) that read their certificates and kubeconfigs from kube-system Secrets
     (selfhosting_volumes.go); the static manifests and their mirror pods go, the self-hosted
     apiserver takes over the embedded store's data directory, and the cluster keeps its
     objects and keeps working."""
-    base = str(tmp_path / "master")
+    base = str(short_tmp / "master")
     port = _free_port()
     try:
         r = _kubeadm("init", "--base-dir", base, "--apiserver-bind-port", str(port), "--node-name", "master-0",
@@ -270,7 +270,7 @@ def test_kubeadm_self_hosting(tmp_path):
                 await c.close()
         asyncio.run(check())
         # an upgrade of a self-hosted component rolls its DaemonSet (no static manifest comes back)
-        newcfg = tmp_path / "upgrade.yaml"
+        newcfg = short_tmp / "upgrade.yaml"
         newcfg.write_text("apiVersion: kubeadm.k8s.io/v1alpha1\nkind: MasterConfiguration\n"
                           "schedulerExtraArgs: {kube-api-qps: '300'}\n")
         admin = os.path.join(base, "admin.conf")

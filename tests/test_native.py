@@ -100,7 +100,7 @@ def test_logpump_records_under_asan(binary, tmp_path):
     assert b"".join(out) == b"".join(chunks[1]) and b"".join(errs) == b"".join(chunks[2])
 
 
-@pytest.mark.skipif(os.geteuid() != 0, reason="mount namespaces need root")
+@pytest.mark.needs_root          # a mount namespace
 def test_nsexec_hides_other_render_nodes(tmp_path):
     dev = tmp_path / "dev"
     (dev / "dri").mkdir(parents=True)

@@ -239,7 +239,7 @@ async def test_service_routes_to_pods_through_userspace_proxy(tmp_path):
                             "readinessProbe": {"tcpSocket": {"port": port}, "periodSeconds": 1}}]}}, "default")
         svc = await c.create({"apiVersion": "v1", "kind": "Service", "metadata": {"name": "web"},
                               "spec": {"type": "NodePort", "selector": {"app": "web"},
-                                       "ports": [{"name": "http", "port": 80, "targetPort": "http"}]}}, "default")
+                                       "ports": [{"name": "http", "port": 8080, "targetPort": "http"}]}}, "default")
         cip, nport = svc["spec"]["clusterIP"], svc["spec"]["ports"][0]["nodePort"]
         assert cip.startswith("127.0.10.") and 31000 <= nport <= 31999
         ep = await _until(lambda: _ready_eps(c, "web"), timeout=30)
@@ -247,7 +247,7 @@ async def test_service_routes_to_pods_through_userspace_proxy(tmp_path):
         proxy = await ProxyServer(Client(lc.api.url), "userspace", node_ip="127.0.0.1", healthz_port=0).start()
         try:
             loop = asyncio.get_running_loop()
-            for url in (f"http://{cip}:80/", f"http://127.0.0.1:{nport}/"):
+            for url in (f"http://{cip}:8080/", f"http://127.0.0.1:{nport}/"):
                 body = await loop.run_in_executor(None, lambda u=url: urllib.request.urlopen(u, timeout=5).read())
                 assert b"Directory listing" in body, url
             hz = await loop.run_in_executor(None, lambda: urllib.request.urlopen(
@@ -258,7 +258,7 @@ async def test_service_routes_to_pods_through_userspace_proxy(tmp_path):
             await _until(lambda: _gone(c, "endpoints", "web"))
             await _until(lambda: _true(not proxy.proxier.sockets or all(s.name != "web" for s in proxy.proxier.sockets)))
             with pytest.raises(OSError):
-                await loop.run_in_executor(None, lambda: urllib.request.urlopen(f"http://{cip}:80/", timeout=2).read())
+                await loop.run_in_executor(None, lambda: urllib.request.urlopen(f"http://{cip}:8080/", timeout=2).read())
         finally:
             await proxy.stop()
             await proxy.client.close()

@@ -20,10 +20,10 @@ def _shim_kw(tmp_path):
     return {"rkt": FAKE, "rkt_env": {"FAKE_RKT_DIR": str(tmp_path / "rkt")}}
 
 
-def test_cri_over_rkt(tmp_path):
+def test_cri_over_rkt(tmp_path, short_tmp):
     async def go():
-        shim = await RktShim(str(tmp_path / "rkt.sock"), str(tmp_path / "state"), **_shim_kw(tmp_path)).start()
-        cri = await CRIClient(str(tmp_path / "rkt.sock")).connect()
+        shim = await RktShim(str(short_tmp / "rkt.sock"), str(tmp_path / "state"), **_shim_kw(tmp_path)).start()
+        cri = await CRIClient(str(short_tmp / "rkt.sock")).connect()
         try:
             v = await cri.version()
             assert v.runtime_name == "rkt" and v.runtime_version == "1.30.0"

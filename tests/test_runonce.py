@@ -20,14 +20,14 @@ def _manifests(d):
                                    "  - {name: c, image: no-such-image:latest, command: [sleep, '30']}\n")
 
 
-def test_run_once_runs_static_pods_without_api(tmp_path):
-    _manifests(tmp_path / "manifests")
+def test_run_once_runs_static_pods_without_api(short_tmp):
+    _manifests(short_tmp / "manifests")
 
     async def go():
-        shim = await RocShim(str(tmp_path / "cri.sock"), str(tmp_path / "shim")).start()
+        shim = await RocShim(str(short_tmp / "cri.sock"), str(short_tmp / "shim"), hooks_dir=str(short_tmp / "hooks.d")).start()
         try:
-            cfg = KubeletConfig(node_name="lonely", root_dir=str(tmp_path / "kubelet"), plugins_dir=str(tmp_path / "plugins"),
-                                cri_socket=str(tmp_path / "cri.sock"), pod_manifest_path=str(tmp_path / "manifests"),
+            cfg = KubeletConfig(node_name="lonely", root_dir=str(short_tmp / "kubelet"), plugins_dir=str(short_tmp / "plugins"),
+                                cri_socket=str(short_tmp / "cri.sock"), pod_manifest_path=str(short_tmp / "manifests"),
                                 volume_mounter="none")
             k = await start_standalone(Kubelet(NullClient(), cfg))
             res = {r["pod"]: r["error"] for r in await run_once(k, retries=3, delay=0.05)}
@@ -41,27 +41,28 @@ def test_run_once_runs_static_pods_without_api(tmp_path):
     run(go(), 60)
 
 
-def test_runonce_command_exit_status(tmp_path):
-    _manifests(tmp_path / "manifests")
-    shim = subprocess.Popen([sys.executable, "-m", "amdkube", "rocshim", "--listen", str(tmp_path / "cri.sock"),
-                             "--state-dir", str(tmp_path / "shim")], cwd=ROOT, stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL)
+def test_runonce_command_exit_status(short_tmp):
+    _manifests(short_tmp / "manifests")
+    shim = subprocess.Popen([sys.executable, "-m", "amdkube", "rocshim", "--listen", str(short_tmp / "cri.sock"),
+                             "--state-dir", str(short_tmp / "shim"), "--hooks-dir", str(short_tmp / "hooks.d")],
+                            cwd=ROOT, stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL)
     try:
         for _ in range(200):
-            if os.path.exists(tmp_path / "cri.sock"):
+            if os.path.exists(short_tmp / "cri.sock"):
                 break
             import time
             time.sleep(0.05)
-        os.remove(tmp_path / "manifests" / "broken.yaml")
+        os.remove(short_tmp / "manifests" / "broken.yaml")
         r = subprocess.run([sys.executable, "-m", "amdkube", "kubelet", "--runonce", "--pod-manifest-path",
-                            str(tmp_path / "manifests"), "--root-dir", str(tmp_path / "kubelet"), "--container-runtime-endpoint",
-                            str(tmp_path / "cri.sock"), "--hostname-override", "n1", "--port", "0"],
+                            str(short_tmp / "manifests"), "--root-dir", str(short_tmp / "kubelet"), "--container-runtime-endpoint",
+                            str(short_tmp / "cri.sock"), "--hostname-override", "n1", "--port", "0"],
                            cwd=ROOT, capture_output=True, text=True, timeout=60)
         assert r.returncode == 0, r.stderr[-2000:]
         assert [json.loads(x) for x in r.stdout.split("\n") if x.startswith("{")] == [{"pod": "web-n1", "error": None}]
     finally:
         shim.terminate()
         shim.wait(10)
-        _kill_runtime_leftovers(tmp_path / "shim")
+        _kill_runtime_leftovers(short_tmp / "shim")
 
 
 def _kill_runtime_leftovers(state_dir):

@@ -9,6 +9,7 @@ import stat
 import textwrap
 
 import grpc
+import pytest
 
 from amdkube.api import meta as m
 from amdkube.grpcdesc.csi import CSI
@@ -460,6 +461,7 @@ def _can_mount_tmpfs(tmp_path) -> bool:
     return True
 
 
+@pytest.mark.needs_root          # mount(2)
 def test_real_tmpfs_mounts_for_secret_and_memory_volumes(tmp_path):
     """With a privileged kubelet (system mounter) secret content lives on tmpfs, never on disk,
     and memory-medium emptyDirs are tmpfs; both are unmounted when the pod goes."""
