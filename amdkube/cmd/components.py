@@ -879,14 +879,15 @@ def rocshim(argv):
     _run_forever(mk)
 
 
-def device_plugin(argv):
+def device_plugin_parser():
     ap = argparse.ArgumentParser("amdkube amd-device-plugin")
     ap.add_argument("--backend", default="auto", help="amdsmi|sysfs|fake|auto")
     ap.add_argument("--fixture", default=None)
     ap.add_argument("--plugins-dir", default="/var/lib/kubelet/device-plugin/plugins")
     ap.add_argument("--resource-name", default="amd.com/gpu")
     ap.add_argument("--health-interval", type=float, default=10.0)
-    ap.add_argument("--health-probe", default="none", choices=("none", "hbm"))
+    ap.add_argument("--health-probe", default="none", choices=("none", "hbm", "mfma", "hbm,mfma"),
+                    help="on-device checks before a GPU is advertised: HBM pattern probe, matrix-core check")
     ap.add_argument("--max-gpus", type=int, default=None, help="advertise only the first N physical GPUs")
     ap.add_argument("--resource-naming", default="single", choices=("single", "mixed"),
                     help="partitioned GPUs: single=amd.com/gpu for all, mixed=amd.com/<cpx>_<nps> per partition type")
@@ -896,7 +897,11 @@ def device_plugin(argv):
                     help="checkpoint of RAS baselines and GPU faults (default: <plugins-dir>/../amdkube-gpu-health.json; "
                          "'' keeps health state in memory only)")
     ap.add_argument("-v", type=int, default=0)
-    a = ap.parse_args(argv)
+    return ap
+
+
+def device_plugin(argv):
+    a = device_plugin_parser().parse_args(argv)
     klog.setup(a.v, "amd-device-plugin")
     state = a.health_state_file if a.health_state_file is not None else \
         os.path.join(os.path.dirname(os.path.abspath(a.plugins_dir)), "amdkube-gpu-health.json")

@@ -135,6 +135,25 @@ def _attr_value(why: str) -> str:
     return v[:63].rstrip("-_.") or "unhealthy"
 
 
+# on-device health probes, in the order they run: name → (binary under BIN_DIR, arguments)
+HEALTH_PROBES = {
+    "hbm": ("hbm-probe", ["--mib", "512", "--iters", "2"]),       # HBM pattern write / copy / verify
+    "mfma": ("mfma-check", ["--ms", "200"]),                       # matrix cores: every MFMA result compared
+}
+
+
+def parse_health_probe(spec: str) -> list[str]:
+    """`none`, or a comma list over HEALTH_PROBES → the probes to run, HBM first."""
+    names = [p.strip() for p in str(spec).split(",")]
+    if names == ["none"]:
+        return []
+    bad = [p for p in names if p not in HEALTH_PROBES]
+    if bad:
+        raise ValueError(f"unknown health probe {bad[0]!r} in {spec!r}: expected none or a comma list of "
+                         f"{', '.join(HEALTH_PROBES)}")
+    return [p for p in HEALTH_PROBES if p in names]
+
+
 class AMDGPUPlugin(DevicePluginServer):
     def __init__(self, backend: Backend, resource_name: str = RESOURCE, plugins_dir: str = DEVICE_PLUGINS_PATH,
                  health_interval: float = 10.0, health_probe: str = "none", dev_root: str = "/dev",
@@ -144,6 +163,7 @@ class AMDGPUPlugin(DevicePluginServer):
         self.backend = backend
         self.health_interval = health_interval
         self.health_probe = health_probe
+        self.probes = parse_health_probe(health_probe)
         self.dev_root = dev_root
         self.ecc_threshold = ecc_threshold
         self.expose_card = expose_card
@@ -174,7 +194,7 @@ class AMDGPUPlugin(DevicePluginServer):
     async def start(self):
         for g in self.gpus:             # the RAS baseline new faults are judged against
             self.monitor.snapshot(g["index"])
-        if self.health_probe != "none":
+        if self.probes:
             await self._probe_all()
         self._check_health(push=False)
         await super().start()
@@ -246,19 +266,23 @@ class AMDGPUPlugin(DevicePluginServer):
                 log.error("health check failed: %s", e)
 
     async def _probe_all(self):
-        """Run the HBM pattern probe on each GPU (subprocess → isolated HIP context)."""
-        binp = os.path.join(BIN_DIR, "hbm-probe")
+        """Run the configured on-device probes (HBM pattern, matrix-core check) on each GPU
+        (subprocess → isolated HIP context); the first failure takes the GPU out of service."""
         for g in self.gpus:
             did = device_id(g)
             env = {k: v for k, v in os.environ.items() if k not in ("HIP_VISIBLE_DEVICES", "CUDA_VISIBLE_DEVICES")}
             env["ROCR_VISIBLE_DEVICES"] = visibility_token(g)
-            try:
-                r = await asyncio.to_thread(subprocess.run, [binp, "--mib", "512", "--iters", "2"], env=env,
-                                            capture_output=True, text=True, timeout=60)
-                if r.returncode != 0:
-                    self.reasons[did] = f"probe: hbm-probe failed rc={r.returncode} {r.stdout.strip()[-200:]}"
-            except Exception as e:
-                self.reasons[did] = f"probe: {e}"
+            for probe in self.probes:
+                name, args = HEALTH_PROBES[probe]
+                try:
+                    r = await asyncio.to_thread(subprocess.run, [os.path.join(BIN_DIR, name), *args], env=env,
+                                                capture_output=True, text=True, timeout=60)
+                    if r.returncode != 0:
+                        self.reasons[did] = f"probe: {name} failed rc={r.returncode} {r.stdout.strip()[-200:]}"
+                except Exception as e:
+                    self.reasons[did] = f"probe: {e}"
+                if self.reasons.get(did, "").startswith("probe:"):
+                    break
 
     # ------------------------------------------------------------ allocation
     def admit_pod(self, pod_name, containers, init_containers):

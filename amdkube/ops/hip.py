@@ -72,6 +72,44 @@ def mfma_tile(a, b, device: int = 0):
     return torch.from_numpy(np.asarray(_need().mfma_tile(bits(a), bits(b), k, device)).copy())
 
 
+def mfma_gemm(a, b, device: int = 0):
+    """C = A @ B with the LDS-staged 64×64 MFMA tile kernel (one workgroup per tile of C): A is M×K,
+    B is K×N, M and N multiples of 64, K a multiple of 16; inputs are rounded to bf16 as the
+    matrix core sees them, the result is fp32."""
+    import numpy as np
+    import torch
+    a = torch.as_tensor(a).to(torch.bfloat16).contiguous()
+    b = torch.as_tensor(b).to(torch.bfloat16).contiguous()
+    if a.dim() != 2 or b.dim() != 2 or a.shape[1] != b.shape[0]:
+        raise ValueError(f"need A MxK and B KxN, got {tuple(a.shape)} and {tuple(b.shape)}")
+    m, k, n = a.shape[0], a.shape[1], b.shape[1]
+    if m <= 0 or n <= 0 or m % 64 or n % 64 or k <= 0 or k % 16:
+        raise ValueError(f"need M and N multiples of 64 and K a multiple of 16, got M={m} N={n} K={k}")
+    bits = lambda t: t.view(torch.int16).numpy().view(np.uint16).ravel()   # noqa: E731
+    return torch.from_numpy(np.asarray(_need().mfma_gemm(bits(a), bits(b), m, n, k, device)).copy())
+
+
+def mfma_check(rounds: int | None = None, ms: float = 50.0, device: int = 0, seed: int = 0x5EED,
+               selftest_flips: int = 0) -> dict:
+    """The matrix-core integrity check (mfma-check in process): every workgroup's MFMA product is
+    compared with exact int32 arithmetic in round 0 and bitwise with round 0 afterwards. `rounds`
+    runs exactly that many, otherwise the run is calibrated to ~`ms`. `selftest_flips` perturbs
+    that many compared values, which the check must then report."""
+    if rounds is not None and rounds < 1:
+        raise ValueError("rounds must be at least 1")
+    r = dict(_need().mfma_check(int(rounds or 0), float(ms), device, seed, selftest_flips))
+    r["first_errors"] = [dict(e) for e in r["first_errors"]]
+    return r
+
+
+def mfma_check_tile(block: int, seed: int = 0x5EED, device: int = 0):
+    """(A, B, C) of one workgroup of the check: its hashed 64×K and K×64 operands and the 64×64
+    round-0 MFMA result, as fp32 tensors."""
+    import numpy as np
+    import torch
+    return tuple(torch.from_numpy(np.asarray(x).copy()) for x in _need().mfma_check_tile(block, seed, device))
+
+
 def hbm_pattern(n16: int, seed: int = 0x5EED, device: int = 0):
     """The HBM probe's write pattern for n16 16-byte words, as uint32 words."""
     import numpy as np

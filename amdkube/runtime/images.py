@@ -54,6 +54,7 @@ def builtin_images() -> dict[str, dict]:
         "amdkube/rocm-vector-add:latest": {"entrypoint": [_b("rocm-vector-add")]},
         "amdkube/hbm-probe:latest": {"entrypoint": [_b("hbm-probe")]},
         "amdkube/gpu-burn:latest": {"entrypoint": [_b("gpu-burn")]},
+        "amdkube/mfma-check:latest": {"entrypoint": [_b("mfma-check")]},
         "amdkube/xgmi-probe:latest": {"entrypoint": [_b("xgmi-probe")]},
         "busybox:latest": {"entrypoint": [sh]},
         "python:3": {"entrypoint": [py]},

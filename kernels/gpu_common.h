@@ -3,8 +3,8 @@
 // The reference's only GPU workload is the CUDA-samples vectorAdd image its e2e tests run
 // in GPU pods (test/images/cuda-vector-add/Dockerfile:15-26; 50,000 fp32 elements), plus
 // device health that comes solely from the plugin (api.proto:97). amdkube replaces that
-// with three CDNA4-native kernels shared by the standalone pod binaries (rocm-vector-add,
-// hbm-probe, gpu-burn) and the in-process Python extension (_hipops):
+// with four CDNA4-native kernels shared by the standalone pod binaries (rocm-vector-add,
+// hbm-probe, gpu-burn, mfma-check) and the in-process Python extension (_hipops):
 //
 //   vector add   wave64 grid-stride, 16-B (float4) loads, grid sized to the chip
 //   HBM probe    address-hashed write / verify / read / copy over buffers larger than
@@ -13,6 +13,8 @@
 //                ~6.3 TB/s; verify counts mismatches (ECC-sensitive health check)
 //   MFMA burn    register-resident v_mfma_f32_32x32x16_bf16 chains, 2 independent
 //                accumulators per wave, for matrix-core load / utilisation validation
+//   MFMA check   (mfma_check.h) LDS-staged 64x64 bf16 tiles whose every result is compared:
+//                round 0 with exact int32 arithmetic, later rounds bitwise with round 0
 //
 // Every launch is bounded by construction (grid-stride loops over checked sizes) and uses
 // no inter-workgroup synchronisation, so no launch can hang the device.
@@ -546,3 +548,5 @@ inline BurnResult run_mfma_burn(double target_ms, int dev) {
 }
 
 }  // namespace amdkube
+
+#include "mfma_check.h"  // the checked matrix-core workload: mfma_gemm_kernel, mfma_check_kernel, their runners

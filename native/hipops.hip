@@ -12,7 +12,7 @@
 namespace py = pybind11;
 
 PYBIND11_MODULE(_hipops, m) {
-  m.doc() = "amdkube HIP (gfx950) validation kernels: vector add, HBM probe, MFMA burn";
+  m.doc() = "amdkube HIP (gfx950) validation kernels: vector add, HBM probe, MFMA burn, MFMA check";
   m.def("device_count", []() {
     int n = 0;
     AK_HIP(hipGetDeviceCount(&n));
@@ -123,6 +123,64 @@ PYBIND11_MODULE(_hipops, m) {
         return py::array_t<float>({32, 32}, c.data());
       },
       py::arg("a_bits"), py::arg("b_bits"), py::arg("k"), py::arg("device") = 0);
+  m.def(
+      "mfma_gemm",
+      [](py::array_t<uint16_t, py::array::c_style | py::array::forcecast> a_bits,
+         py::array_t<uint16_t, py::array::c_style | py::array::forcecast> b_bits, int mm, int nn, int k, int dev) {
+        std::vector<uint16_t> a(a_bits.data(), a_bits.data() + a_bits.size()), b(b_bits.data(), b_bits.data() + b_bits.size());
+        std::vector<float> c;
+        {
+          py::gil_scoped_release nogil;
+          c = amdkube::mfma_gemm_host(a, b, mm, nn, k, dev);
+        }
+        return py::array_t<float>({mm, nn}, c.data());
+      },
+      py::arg("a_bits"), py::arg("b_bits"), py::arg("m"), py::arg("n"), py::arg("k"), py::arg("device") = 0);
+  m.def(
+      "mfma_check",
+      [](int rounds, double ms, int dev, uint32_t seed, int flips) {
+        amdkube::MfmaCheckResult r;
+        {
+          py::gil_scoped_release nogil;
+          r = amdkube::run_mfma_check(rounds, ms, dev, seed, flips);
+        }
+        py::list recs;
+        for (const amdkube::MfmaCheckRecord& e : r.first_errors) {
+          py::dict d;
+          d["block"] = e.block;
+          d["row"] = e.row;
+          d["col"] = e.col;
+          d["round"] = e.round;
+          d["got"] = e.got;
+          d["want"] = e.want;
+          recs.append(d);
+        }
+        py::dict o;
+        o["ok"] = r.errors == 0;
+        o["errors"] = r.errors;
+        o["rounds"] = r.rounds;
+        o["blocks"] = r.blocks;
+        o["k"] = r.k;
+        o["ms"] = r.ms;
+        o["bf16_tflops"] = r.tflops;
+        o["first_errors"] = recs;
+        return o;
+      },
+      py::arg("rounds") = 0, py::arg("ms") = 50.0, py::arg("device") = 0, py::arg("seed") = 0x5eedu,
+      py::arg("selftest_flips") = 0);
+  m.def(
+      "mfma_check_tile",
+      [](int block, uint32_t seed, int dev) {
+        amdkube::MfmaCheckTile t;
+        {
+          py::gil_scoped_release nogil;
+          t = amdkube::mfma_check_tile_host(block, seed, dev);
+        }
+        return py::make_tuple(py::array_t<float>({amdkube::MFMA_TILE, t.k}, t.a.data()),
+                              py::array_t<float>({t.k, amdkube::MFMA_TILE}, t.b.data()),
+                              py::array_t<float>({amdkube::MFMA_TILE, amdkube::MFMA_TILE}, t.c.data()));
+      },
+      py::arg("block"), py::arg("seed") = 0x5eedu, py::arg("device") = 0);
   m.def(
       "mfma_burn",
       [](double ms, int dev) {
