@@ -886,8 +886,16 @@ def device_plugin_parser():
     ap.add_argument("--plugins-dir", default="/var/lib/kubelet/device-plugin/plugins")
     ap.add_argument("--resource-name", default="amd.com/gpu")
     ap.add_argument("--health-interval", type=float, default=10.0)
-    ap.add_argument("--health-probe", default="none", choices=("none", "hbm", "mfma", "hbm,mfma"),
-                    help="on-device checks before a GPU is advertised: HBM pattern probe, matrix-core check")
+    def health_probe(spec):
+        from ..deviceplugin.amd import parse_health_probe
+        try:
+            parse_health_probe(spec)
+        except ValueError as e:
+            raise argparse.ArgumentTypeError(str(e))
+        return spec
+    ap.add_argument("--health-probe", default="none", type=health_probe, metavar="LIST",
+                    help="on-device checks before a GPU is advertised: none, or a comma list over hbm (HBM pattern "
+                         "probe), mfma (bf16 matrix-core check) and mfma-lp (FP8 / MXFP8 / MXFP4 matrix-core check)")
     ap.add_argument("--max-gpus", type=int, default=None, help="advertise only the first N physical GPUs")
     ap.add_argument("--resource-naming", default="single", choices=("single", "mixed"),
                     help="partitioned GPUs: single=amd.com/gpu for all, mixed=amd.com/<cpx>_<nps> per partition type")

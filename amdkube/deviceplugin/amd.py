@@ -1,5 +1,6 @@
 """The AMD Instinct (MI355X) device plugin: advertises `amd.com/gpu` with device attributes,
-tracks health from amd-smi RAS/ECC counters (plus an optional on-device HBM pattern probe),
+tracks health from amd-smi RAS/ECC counters (plus optional on-device probes: the HBM pattern probe,
+the bf16 matrix-core check `mfma` and its FP8 / MXFP8 / MXFP4 counterpart `mfma-lp`),
 and injects /dev/kfd + the GPU's DRM render node into containers.
 
 Replaces the out-of-tree NVIDIA plugin the reference's DaemonSet deploys
@@ -139,6 +140,8 @@ def _attr_value(why: str) -> str:
 HEALTH_PROBES = {
     "hbm": ("hbm-probe", ["--mib", "512", "--iters", "2"]),       # HBM pattern write / copy / verify
     "mfma": ("mfma-check", ["--ms", "200"]),                       # matrix cores: every MFMA result compared
+    # the low-precision matrix-core paths inference pods run: FP8 and the block-scaled MXFP8 / MXFP4 forms
+    "mfma-lp": ("mfma-check", ["--dtype", "fp8,mxfp8,mxfp4", "--ms", "200"]),
 }
 
 
@@ -266,7 +269,7 @@ class AMDGPUPlugin(DevicePluginServer):
                 log.error("health check failed: %s", e)
 
     async def _probe_all(self):
-        """Run the configured on-device probes (HBM pattern, matrix-core check) on each GPU
+        """Run the configured on-device probes (HBM pattern, matrix-core checks) on each GPU
         (subprocess → isolated HIP context); the first failure takes the GPU out of service."""
         for g in self.gpus:
             did = device_id(g)

@@ -89,25 +89,92 @@ def mfma_gemm(a, b, device: int = 0):
     return torch.from_numpy(np.asarray(_need().mfma_gemm(bits(a), bits(b), m, n, k, device)).copy())
 
 
+LP_DTYPES = ("fp8", "mxfp8", "mxfp4")     # the low-precision matrix-core paths (kernels/mfma_check_lp.h)
+
+
+def _codes(x, what):
+    import numpy as np
+    x = _np(x, None)
+    if x.dtype != np.uint8 or x.ndim != 2:
+        raise ValueError(f"{what} must be a 2-D uint8 array, got {x.dtype} {x.shape}")
+    return x
+
+
+def _gemm_lp(dtype, a, b, sa, sb, device):
+    import numpy as np
+    import torch
+    m, k, n = a.shape[0], a.shape[1], b.shape[1]
+    kstep = 16 if dtype == "fp8" else 64
+    if b.shape[0] != k:
+        raise ValueError(f"need A MxK and B KxN, got {a.shape} and {b.shape}")
+    if m <= 0 or n <= 0 or m % 64 or n % 64 or k <= 0 or k % kstep:
+        raise ValueError(f"need M and N multiples of 64 and K a multiple of {kstep}, got M={m} N={n} K={k}")
+    if dtype == "fp8":
+        sa = sb = np.zeros(0, np.uint8)
+    elif sa.shape != (m, k // 32) or sb.shape != (k // 32, n):
+        raise ValueError(f"need A scales Mx(K/32) and B scales (K/32)xN, got {sa.shape} and {sb.shape}")
+    if dtype == "mxfp4" and (int(a.max()) > 15 or int(b.max()) > 15):
+        raise ValueError("e2m1 codes must be in [0, 15]")
+    c = _need().mfma_gemm_lp(dtype, a.ravel(), b.ravel(), sa.ravel(), sb.ravel(), m, n, k, device)
+    return torch.from_numpy(np.asarray(c).copy())
+
+
+def mfma_gemm_fp8(a, b, device: int = 0):
+    """C = A @ B with the LDS-staged 64×64 tile kernel on v_mfma_f32_32x32x16_fp8_fp8: A is M×K, B is
+    K×N, M and N multiples of 64, K a multiple of 16; inputs are rounded to OCP e4m3fn as the matrix
+    core sees them, the result is fp32."""
+    import torch
+    from . import lowp
+    a, b = torch.as_tensor(a), torch.as_tensor(b)
+    if a.dim() != 2 or b.dim() != 2:
+        raise ValueError(f"need A MxK and B KxN, got {tuple(a.shape)} and {tuple(b.shape)}")
+    return _gemm_lp("fp8", lowp.encode_e4m3(a), lowp.encode_e4m3(b), None, None, device)
+
+
+def mfma_gemm_mx(a_codes, a_scales, b_codes, b_scales, fmt: str, device: int = 0):
+    """C = A @ B with the block-scaled v_mfma_scale_f32_32x32x64_f8f6f4 tile kernel. `fmt` is "fp8"
+    (e4m3fn codes) or "fp4" (e2m1 codes, 0..15), one code per uint8; the E8M0 scales are uint8, A's as
+    M×K/32 and B's as K/32×N (amdkube.ops.lowp.mx_quantize along K). M and N multiples of 64, K a
+    multiple of 64; the result is an fp32 tensor."""
+    if fmt not in ("fp8", "fp4"):
+        raise ValueError(f"unknown MX element format {fmt!r}: expected fp8 or fp4")
+    return _gemm_lp("mx" + fmt, _codes(a_codes, "A codes"), _codes(b_codes, "B codes"), _codes(a_scales, "A scales"),
+                    _codes(b_scales, "B scales"), device)
+
+
+def _check_dtype(dtype):
+    if dtype != "bf16" and dtype not in LP_DTYPES:
+        raise ValueError(f"unknown dtype {dtype!r}: expected bf16, {', '.join(LP_DTYPES)}")
+
+
 def mfma_check(rounds: int | None = None, ms: float = 50.0, device: int = 0, seed: int = 0x5EED,
-               selftest_flips: int = 0) -> dict:
+               selftest_flips: int = 0, dtype: str = "bf16") -> dict:
     """The matrix-core integrity check (mfma-check in process): every workgroup's MFMA product is
-    compared with exact int32 arithmetic in round 0 and bitwise with round 0 afterwards. `rounds`
+    compared with exact integer arithmetic in round 0 and bitwise with round 0 afterwards. `rounds`
     runs exactly that many, otherwise the run is calibrated to ~`ms`. `selftest_flips` perturbs
-    that many compared values, which the check must then report."""
+    that many compared values, which the check must then report. `dtype` picks the matrix-core path:
+    bf16, fp8, mxfp8 or mxfp4; the result carries `dtype` and `tflops` (bf16 also `bf16_tflops`)."""
+    _check_dtype(dtype)
     if rounds is not None and rounds < 1:
         raise ValueError("rounds must be at least 1")
-    r = dict(_need().mfma_check(int(rounds or 0), float(ms), device, seed, selftest_flips))
+    if dtype == "bf16":
+        r = dict(_need().mfma_check(int(rounds or 0), float(ms), device, seed, selftest_flips))
+        r["dtype"], r["tflops"] = "bf16", r["bf16_tflops"]
+    else:
+        r = dict(_need().mfma_check_lp(dtype, int(rounds or 0), float(ms), device, seed, selftest_flips))
     r["first_errors"] = [dict(e) for e in r["first_errors"]]
     return r
 
 
-def mfma_check_tile(block: int, seed: int = 0x5EED, device: int = 0):
-    """(A, B, C) of one workgroup of the check: its hashed 64×K and K×64 operands and the 64×64
-    round-0 MFMA result, as fp32 tensors."""
+def mfma_check_tile(block: int, seed: int = 0x5EED, device: int = 0, dtype: str = "bf16"):
+    """(A, B, C) of one workgroup of the check: its hashed 64×K and K×64 operands (decoded, with the
+    block scales applied for the MX dtypes) and the 64×64 round-0 MFMA result, as fp32 tensors."""
     import numpy as np
     import torch
-    return tuple(torch.from_numpy(np.asarray(x).copy()) for x in _need().mfma_check_tile(block, seed, device))
+    _check_dtype(dtype)
+    ext = _need()
+    t = ext.mfma_check_tile(block, seed, device) if dtype == "bf16" else ext.mfma_check_lp_tile(dtype, block, seed, device)
+    return tuple(torch.from_numpy(np.asarray(x).copy()) for x in t)
 
 
 def hbm_pattern(n16: int, seed: int = 0x5EED, device: int = 0):

@@ -14,7 +14,8 @@
 //   MFMA burn    register-resident v_mfma_f32_32x32x16_bf16 chains, 2 independent
 //                accumulators per wave, for matrix-core load / utilisation validation
 //   MFMA check   (mfma_check.h) LDS-staged 64x64 bf16 tiles whose every result is compared:
-//                round 0 with exact int32 arithmetic, later rounds bitwise with round 0
+//                round 0 with exact int32 arithmetic, later rounds bitwise with round 0;
+//                (mfma_check_lp.h) the same on the FP8 MFMA and the block-scaled MXFP8 / MXFP4 forms
 //
 // Every launch is bounded by construction (grid-stride loops over checked sizes) and uses
 // no inter-workgroup synchronisation, so no launch can hang the device.
@@ -550,3 +551,4 @@ inline BurnResult run_mfma_burn(double target_ms, int dev) {
 }  // namespace amdkube
 
 #include "mfma_check.h"  // the checked matrix-core workload: mfma_gemm_kernel, mfma_check_kernel, their runners
+#include "mfma_check_lp.h"  // the same for the FP8, MXFP8 and MXFP4 matrix-core paths

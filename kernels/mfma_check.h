@@ -286,11 +286,10 @@ struct MfmaCheckRun {
 
 // rounds > 0: one launch of exactly that many rounds. rounds <= 0: calibrate to ~target_ms as
 // run_mfma_burn does (the self-test flips then go into the last launch only).
-inline MfmaCheckResult run_mfma_check(int rounds, double target_ms, int dev, uint32_t seed = 0x5eedu, int flips = 0,
-                                      int k_total = MFMA_CHECK_KMAX) {
-  if (flips < 0 || flips > MFMA_CHECK_MAX_FLIPS) throw std::invalid_argument("selftest flips must be in [0, 4096]");
-  AK_HIP(hipSetDevice(dev));
-  MfmaCheckRun run(dev, seed, k_total);
+// Shared by the low-precision checks (mfma_check_lp.h): Run provides launch(rounds, flips), blocks, k
+// and the errors / nrec / recs buffers.
+template <class Run>
+inline MfmaCheckResult mfma_check_drive(Run& run, int rounds, double target_ms, int flips) {
   hipEvent_t e0, e1;
   AK_HIP(hipEventCreate(&e0));
   AK_HIP(hipEventCreate(&e1));
@@ -339,14 +338,22 @@ inline MfmaCheckResult run_mfma_check(int rounds, double target_ms, int dev, uin
   return r;
 }
 
+inline MfmaCheckResult run_mfma_check(int rounds, double target_ms, int dev, uint32_t seed = 0x5eedu, int flips = 0,
+                                      int k_total = MFMA_CHECK_KMAX) {
+  if (flips < 0 || flips > MFMA_CHECK_MAX_FLIPS) throw std::invalid_argument("selftest flips must be in [0, 4096]");
+  AK_HIP(hipSetDevice(dev));
+  MfmaCheckRun run(dev, seed, k_total);
+  return mfma_check_drive(run, rounds, target_ms, flips);
+}
+
 struct MfmaCheckTile {
   int k = 0;
   std::vector<float> a, b, c;  // A[64 x k], B[k x 64], round-0 C[64 x 64] of one workgroup
 };
 
-inline MfmaCheckTile mfma_check_tile_host(int block, uint32_t seed, int dev, int k_total = MFMA_CHECK_KMAX) {
-  AK_HIP(hipSetDevice(dev));
-  MfmaCheckRun run(dev, seed, k_total);
+// one launch of a single round with workgroup `block` storing its operands and product
+template <class Run>
+inline MfmaCheckTile mfma_check_fetch_tile(Run& run, int block) {
   if (block < 0 || block >= run.blocks) throw std::invalid_argument("block out of range");
   MfmaCheckTile t;
   t.k = run.k;
@@ -360,6 +367,12 @@ inline MfmaCheckTile mfma_check_tile_host(int block, uint32_t seed, int dev, int
   AK_HIP(hipMemcpy(t.b.data(), db.p, nab * sizeof(float), hipMemcpyDeviceToHost));
   AK_HIP(hipMemcpy(t.c.data(), dc.p, nc * sizeof(float), hipMemcpyDeviceToHost));
   return t;
+}
+
+inline MfmaCheckTile mfma_check_tile_host(int block, uint32_t seed, int dev, int k_total = MFMA_CHECK_KMAX) {
+  AK_HIP(hipSetDevice(dev));
+  MfmaCheckRun run(dev, seed, k_total);
+  return mfma_check_fetch_tile(run, block);
 }
 
 }  // namespace amdkube

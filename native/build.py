@@ -108,8 +108,9 @@ def targets(sanitize=False, cpu_only=False):
         ho = [hip, f"--offload-arch={ARCH}", "-O3", "-std=c++17"]
         hdr = n("kernels/gpu_common.h")
         chk = n("kernels/mfma_check.h")      # included by gpu_common.h
+        lp = n("kernels/mfma_check_lp.h")    # included by gpu_common.h
         t += [
-            (n(OUT, "_hipops" + EXT), [n("native/hipops.hip"), hdr, chk],
+            (n(OUT, "_hipops" + EXT), [n("native/hipops.hip"), hdr, chk, lp],
              [*ho, "-shared", "-fPIC", *py, n("native/hipops.hip"), "-o", "{out}"]),
             (n(BIN, "rocm-vector-add"), [n("kernels/vector_add.hip"), hdr], [*ho, n("kernels/vector_add.hip"), "-o", "{out}"]),
             # the HIP-free pod workload: a bare gfx950 code object, then the HSA host embedding it
@@ -120,8 +121,8 @@ def targets(sanitize=False, cpu_only=False):
               f'-I{ROCM}/include {n("kernels/hsa_vector_add.cpp")} -L{ROCM}/lib -Wl,-rpath,{ROCM}/lib -lhsa-runtime64 -o "$1"',
               hip, "{out}"]),
             (n(BIN, "hbm-probe"), [n("kernels/hbm_probe.hip"), hdr], [*ho, n("kernels/hbm_probe.hip"), "-o", "{out}"]),
-            (n(BIN, "gpu-burn"), [n("kernels/gpu_burn.hip"), hdr, chk], [*ho, n("kernels/gpu_burn.hip"), "-o", "{out}"]),
-            (n(BIN, "mfma-check"), [n("kernels/mfma_check.hip"), hdr, chk],
+            (n(BIN, "gpu-burn"), [n("kernels/gpu_burn.hip"), hdr, chk, lp], [*ho, n("kernels/gpu_burn.hip"), "-o", "{out}"]),
+            (n(BIN, "mfma-check"), [n("kernels/mfma_check.hip"), hdr, chk, lp],
              [*ho, n("kernels/mfma_check.hip"), "-o", "{out}"]),
             (n(BIN, "xgmi-probe"), [n("kernels/xgmi_probe.cpp")],
              [*ho, "-x", "hip", n("kernels/xgmi_probe.cpp"), *rocm_inc, *rpath, "-lrccl", "-o", "{out}"]),

@@ -11,6 +11,34 @@
 
 namespace py = pybind11;
 
+// the result of a check run, with its rate under `rate_key`
+static py::dict check_result(const amdkube::MfmaCheckResult& r, const char* rate_key) {
+  py::list recs;
+  for (const amdkube::MfmaCheckRecord& e : r.first_errors) {
+    py::dict d;
+    d["block"] = e.block;
+    d["row"] = e.row;
+    d["col"] = e.col;
+    d["round"] = e.round;
+    d["got"] = e.got;
+    d["want"] = e.want;
+    recs.append(d);
+  }
+  py::dict o;
+  o["ok"] = r.errors == 0;
+  o["errors"] = r.errors;
+  o["rounds"] = r.rounds;
+  o["blocks"] = r.blocks;
+  o["k"] = r.k;
+  o["ms"] = r.ms;
+  o[rate_key] = r.tflops;
+  o["first_errors"] = recs;
+  return o;
+}
+
+using bytes_in = py::array_t<uint8_t, py::array::c_style | py::array::forcecast>;
+static std::vector<uint8_t> to_vec(const bytes_in& x) { return std::vector<uint8_t>(x.data(), x.data() + x.size()); }
+
 PYBIND11_MODULE(_hipops, m) {
   m.doc() = "amdkube HIP (gfx950) validation kernels: vector add, HBM probe, MFMA burn, MFMA check";
   m.def("device_count", []() {
@@ -144,27 +172,7 @@ PYBIND11_MODULE(_hipops, m) {
           py::gil_scoped_release nogil;
           r = amdkube::run_mfma_check(rounds, ms, dev, seed, flips);
         }
-        py::list recs;
-        for (const amdkube::MfmaCheckRecord& e : r.first_errors) {
-          py::dict d;
-          d["block"] = e.block;
-          d["row"] = e.row;
-          d["col"] = e.col;
-          d["round"] = e.round;
-          d["got"] = e.got;
-          d["want"] = e.want;
-          recs.append(d);
-        }
-        py::dict o;
-        o["ok"] = r.errors == 0;
-        o["errors"] = r.errors;
-        o["rounds"] = r.rounds;
-        o["blocks"] = r.blocks;
-        o["k"] = r.k;
-        o["ms"] = r.ms;
-        o["bf16_tflops"] = r.tflops;
-        o["first_errors"] = recs;
-        return o;
+        return check_result(r, "bf16_tflops");
       },
       py::arg("rounds") = 0, py::arg("ms") = 50.0, py::arg("device") = 0, py::arg("seed") = 0x5eedu,
       py::arg("selftest_flips") = 0);
@@ -181,6 +189,51 @@ PYBIND11_MODULE(_hipops, m) {
                               py::array_t<float>({amdkube::MFMA_TILE, amdkube::MFMA_TILE}, t.c.data()));
       },
       py::arg("block"), py::arg("seed") = 0x5eedu, py::arg("device") = 0);
+  // the low-precision matrix-core paths (kernels/mfma_check_lp.h): dtype is fp8, mxfp8 or mxfp4
+  m.def(
+      "mfma_gemm_lp",
+      [](const std::string& dtype, bytes_in a_codes, bytes_in b_codes, bytes_in a_scales, bytes_in b_scales, int mm, int nn,
+         int k, int dev) {
+        const int fmt = amdkube::mfma_lp_fmt(dtype);
+        std::vector<uint8_t> a = to_vec(a_codes), b = to_vec(b_codes), sa = to_vec(a_scales), sb = to_vec(b_scales);
+        std::vector<float> c;
+        {
+          py::gil_scoped_release nogil;
+          c = amdkube::mfma_gemm_lp_host(fmt, a, b, sa, sb, mm, nn, k, dev);
+        }
+        return py::array_t<float>({mm, nn}, c.data());
+      },
+      py::arg("dtype"), py::arg("a_codes"), py::arg("b_codes"), py::arg("a_scales"), py::arg("b_scales"), py::arg("m"),
+      py::arg("n"), py::arg("k"), py::arg("device") = 0);
+  m.def(
+      "mfma_check_lp",
+      [](const std::string& dtype, int rounds, double ms, int dev, uint32_t seed, int flips) {
+        const int fmt = amdkube::mfma_lp_fmt(dtype);
+        amdkube::MfmaCheckResult r;
+        {
+          py::gil_scoped_release nogil;
+          r = amdkube::run_mfma_check_lp(fmt, rounds, ms, dev, seed, flips);
+        }
+        py::dict o = check_result(r, "tflops");
+        o["dtype"] = dtype;
+        return o;
+      },
+      py::arg("dtype"), py::arg("rounds") = 0, py::arg("ms") = 50.0, py::arg("device") = 0, py::arg("seed") = 0x5eedu,
+      py::arg("selftest_flips") = 0);
+  m.def(
+      "mfma_check_lp_tile",
+      [](const std::string& dtype, int block, uint32_t seed, int dev) {
+        const int fmt = amdkube::mfma_lp_fmt(dtype);
+        amdkube::MfmaCheckTile t;
+        {
+          py::gil_scoped_release nogil;
+          t = amdkube::mfma_check_lp_tile_host(fmt, block, seed, dev);
+        }
+        return py::make_tuple(py::array_t<float>({amdkube::MFMA_TILE, t.k}, t.a.data()),
+                              py::array_t<float>({t.k, amdkube::MFMA_TILE}, t.b.data()),
+                              py::array_t<float>({amdkube::MFMA_TILE, amdkube::MFMA_TILE}, t.c.data()));
+      },
+      py::arg("dtype"), py::arg("block"), py::arg("seed") = 0x5eedu, py::arg("device") = 0);
   m.def(
       "mfma_burn",
       [](double ms, int dev) {
