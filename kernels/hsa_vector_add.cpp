@@ -18,13 +18,34 @@
 // user-space teardown but the next process then waits that much longer in the kernel's KFD
 // release path, so the default shuts down cleanly.
 //
-//   hsa-vector-add [-n ELEMENTS] [--print-uuid] [--json] [--expect-devices K] [--fast-exit]
+// What is left of hsa_init after the wait in open("/dev/kfd") is file reading: ROCr reads about
+// 8900 small files one by one (the CPU caches under /sys/devices/system/node, the KFD topology and
+// /proc/cpuinfo, each walked twice; docs/PERFORMANCE.md "Prefetching hsa_init's file reads"). A
+// helper thread started first thing in main reads them during that wait and this executable's
+// fopen serves them to ROCr from memory (native/sysfs_prefetch.h): the part of hsa_init after the
+// wait drops from 53 ms to 16 ms and a back-to-back pod from 280 ms to 240 ms (medians of 15 runs
+// each; bench.py: 248 against 287 ms per step). The helper stops when the open returns, and a file
+// it did not get to is read once by the thread that asks and kept for ROCr's second walk, so a
+// pod with no predecessor, which has no wait to use, still gains (54 ms to 41 ms). --no-prefetch
+// or AMDKUBE_VADD_PREFETCH=0 turn it off. AMDKUBE_VADD_TRACE=1 prints the phase times, hsa_init
+// split at the /dev/kfd open, and its file I/O by path group (AMDKUBE_VADD_TRACE=paths: every
+// path as well).
+//
+//   hsa-vector-add [-n ELEMENTS] [--print-uuid] [--json] [--expect-devices K] [--fast-exit] [--no-prefetch]
 #include <hsa/hsa.h>
 #include <hsa/hsa_ext_amd.h>
 
+#include <dirent.h>
+#include <dlfcn.h>
+#include <fcntl.h>
+#include <pthread.h>
+
 #include <algorithm>
+#include <atomic>
+#include <cerrno>
 #include <chrono>
 #include <cmath>
+#include <cstdarg>
 #include <cstddef>
 #include <cstdint>
 #include <cstdio>
@@ -32,6 +53,8 @@
 #include <cstring>
 #include <string>
 #include <vector>
+
+#include "../native/sysfs_prefetch.h"
 
 #ifndef VADD_CO_PATH
 #error "VADD_CO_PATH must name the gfx950 code object to embed (native/build.py)"
@@ -233,9 +256,185 @@ uint32_t stream_groups(uint64_t floats, uint32_t cus) {
   return static_cast<uint32_t>(want < 1 ? 1 : (want < cap ? want : cap));
 }
 
+// AMDKUBE_VADD_TRACE: where hsa_init's file I/O goes. The executable's fopen/fclose/open/opendir
+// (below) are found before libc's by ROCr's and libdrm's calls; inside the hsa_init window each
+// call is counted and timed into the group its path belongs to, a stdio file from fopen to
+// fclose (sysfs formats its answer in the read, not the open). These run before main() and on
+// ROCr's threads: everything here is constant-initialised.
+namespace iotrace {
+
+enum Group { kTopology, kProc, kSysSystem, kDrmPci, kDev, kOther, kGroups };
+const char* const kGroupName[kGroups] = {"kfd-topology", "/proc", "/sys/devices/system", "drm+pci", "/dev", "other"};
+
+struct Acc {
+  std::atomic<uint64_t> fopens, fopen_ns, opens, open_ns, opendirs, opendir_ns;
+};
+Acc g_acc[kGroups];
+std::atomic<bool> g_window{false};                  // true while main is inside hsa_init with tracing on
+std::atomic<bool> g_paths{false};                   // AMDKUBE_VADD_TRACE=paths: also list every path opened
+bool tracing() { return g_window.load(std::memory_order_acquire) && !amdkube::prefetch::t_in_helper; }
+std::atomic<int64_t> g_kfd_enter_ns{0}, g_kfd_return_ns{0};
+struct Span {
+  FILE* f;
+  int64_t t0;
+  int group;
+};
+Span g_spans[64];                                   // stdio files open right now (ROCr holds one or two)
+pthread_mutex_t g_spans_mu = PTHREAD_MUTEX_INITIALIZER;
+
+int64_t now_ns() {
+  return std::chrono::duration_cast<std::chrono::nanoseconds>(std::chrono::steady_clock::now().time_since_epoch()).count();
+}
+
+bool starts(const char* path, const char* prefix) { return std::strncmp(path, prefix, std::strlen(prefix)) == 0; }
+
+int group_of(const char* path) {
+  if (!path) return kOther;
+  if (starts(path, "/sys/devices/virtual/kfd/kfd/topology")) return kTopology;
+  if (starts(path, "/proc/")) return kProc;
+  if (starts(path, "/sys/devices/system/")) return kSysSystem;
+  if (starts(path, "/sys/class/drm") || starts(path, "/sys/bus/pci") || starts(path, "/sys/devices/pci") ||
+      starts(path, "/sys/dev/char"))
+    return kDrmPci;
+  if (starts(path, "/dev/")) return kDev;
+  return kOther;
+}
+
+void span_begin(FILE* f, int group, int64_t t0) {
+  pthread_mutex_lock(&g_spans_mu);
+  for (Span& s : g_spans)
+    if (!s.f) {
+      s = Span{f, t0, group};
+      break;
+    }
+  pthread_mutex_unlock(&g_spans_mu);
+}
+
+// the span of `f`, if it was opened inside the window: closes it and returns its group, else -1
+int span_end(FILE* f, int64_t* t0) {
+  int group = -1;
+  pthread_mutex_lock(&g_spans_mu);
+  for (Span& s : g_spans)
+    if (s.f == f) {
+      group = s.group;
+      *t0 = s.t0;
+      s.f = nullptr;
+      break;
+    }
+  pthread_mutex_unlock(&g_spans_mu);
+  return group;
+}
+
+template <typename Fn>
+Fn next(std::atomic<Fn>& slot, const char* name) {
+  Fn fn = slot.load(std::memory_order_acquire);
+  if (!fn) {
+    fn = reinterpret_cast<Fn>(dlsym(RTLD_NEXT, name));
+    slot.store(fn, std::memory_order_release);
+  }
+  return fn;
+}
+
+using fclose_fn = int (*)(FILE*);
+using open_fn = int (*)(const char*, int, ...);
+using opendir_fn = DIR* (*)(const char*);
+std::atomic<fclose_fn> g_fclose{nullptr};
+std::atomic<open_fn> g_open{nullptr};
+std::atomic<opendir_fn> g_opendir{nullptr};
+
+void report(int64_t init_begin_ns, int64_t init_end_ns) {
+  const int64_t enter = g_kfd_enter_ns.load(), ret = g_kfd_return_ns.load();
+  if (enter && ret) {
+    std::fprintf(stderr, "[trace] %-14s %8.3f ms\n", "init:pre-open", (enter - init_begin_ns) / 1e6);
+    std::fprintf(stderr, "[trace] %-14s %8.3f ms\n", "init:kfd-wait", (ret - enter) / 1e6);
+    std::fprintf(stderr, "[trace] %-14s %8.3f ms\n", "init:post-wait", (init_end_ns - ret) / 1e6);
+  }
+  for (int g = 0; g < kGroups; ++g) {
+    const Acc& a = g_acc[g];
+    std::fprintf(stderr, "[trace] io %-19s fopen=%llu fopen_ms=%.3f open=%llu open_ms=%.3f opendir=%llu opendir_ms=%.3f\n",
+                 kGroupName[g], static_cast<unsigned long long>(a.fopens.load()), a.fopen_ns.load() / 1e6,
+                 static_cast<unsigned long long>(a.opens.load()), a.open_ns.load() / 1e6,
+                 static_cast<unsigned long long>(a.opendirs.load()), a.opendir_ns.load() / 1e6);
+  }
+}
+
+}  // namespace iotrace
+
 }  // namespace
 
-int main(int argc, char** argv) {
+extern "C" FILE* fopen(const char* path, const char* mode) {
+  if (!iotrace::tracing()) return amdkube::prefetch::open_file(path, mode);
+  const int64_t t0 = iotrace::now_ns();
+  FILE* f = amdkube::prefetch::open_file(path, mode);
+  const int saved = errno;
+  const int g = iotrace::group_of(path);
+  if (iotrace::g_paths.load(std::memory_order_relaxed)) std::fprintf(stderr, "[path] fopen %s %s\n", path ? path : "(null)", f ? "ok" : std::strerror(saved));
+  iotrace::g_acc[g].fopens.fetch_add(1, std::memory_order_relaxed);
+  if (f) iotrace::span_begin(f, g, t0);
+  else iotrace::g_acc[g].fopen_ns.fetch_add(iotrace::now_ns() - t0, std::memory_order_relaxed);
+  errno = saved;
+  return f;
+}
+
+extern "C" int fclose(FILE* f) {
+  const int rc = iotrace::next(iotrace::g_fclose, "fclose")(f);
+  if (iotrace::tracing()) {
+    const int saved = errno;
+    int64_t t0 = 0;
+    const int g = iotrace::span_end(f, &t0);
+    if (g >= 0) iotrace::g_acc[g].fopen_ns.fetch_add(iotrace::now_ns() - t0, std::memory_order_relaxed);
+    errno = saved;
+  }
+  return rc;
+}
+
+extern "C" int open(const char* path, int flags, ...) {
+  mode_t m = 0;
+  if ((flags & O_CREAT) || (flags & O_TMPFILE) == O_TMPFILE) {
+    va_list ap;
+    va_start(ap, flags);
+    m = static_cast<mode_t>(va_arg(ap, int));
+    va_end(ap);
+  }
+  const iotrace::open_fn real = iotrace::next(iotrace::g_open, "open");
+  const bool kfd = path && !std::strcmp(path, "/dev/kfd");
+  if (!iotrace::tracing() && !kfd) return real(path, flags, m);
+  const int64_t t0 = iotrace::now_ns();
+  const int fd = real(path, flags, m);
+  const int saved = errno;
+  const int64_t t1 = iotrace::now_ns();
+  // the wait the prefetch helper works in is over: from here on it would only compete with ROCr's own reads
+  if (kfd) amdkube::prefetch::cancel();
+  if (iotrace::tracing()) {
+    const int g = iotrace::group_of(path);
+    iotrace::g_acc[g].opens.fetch_add(1, std::memory_order_relaxed);
+    iotrace::g_acc[g].open_ns.fetch_add(t1 - t0, std::memory_order_relaxed);
+    if (kfd && !iotrace::g_kfd_enter_ns.load()) {
+      iotrace::g_kfd_enter_ns.store(t0);
+      iotrace::g_kfd_return_ns.store(t1);
+    }
+  }
+  errno = saved;
+  return fd;
+}
+
+extern "C" DIR* opendir(const char* path) {
+  const iotrace::opendir_fn real = iotrace::next(iotrace::g_opendir, "opendir");
+  if (!iotrace::tracing()) return real(path);
+  const int64_t t0 = iotrace::now_ns();
+  DIR* d = real(path);
+  const int saved = errno;
+  const int g = iotrace::group_of(path);
+  if (iotrace::g_paths.load(std::memory_order_relaxed)) std::fprintf(stderr, "[path] opendir %s\n", path ? path : "(null)");
+  iotrace::g_acc[g].opendirs.fetch_add(1, std::memory_order_relaxed);
+  iotrace::g_acc[g].opendir_ns.fetch_add(iotrace::now_ns() - t0, std::memory_order_relaxed);
+  errno = saved;
+  return d;
+}
+
+namespace {
+
+int run(int argc, char** argv, bool prefetch) {
   size_t n = 50000;
   bool print_uuid = false, json = false, shutdown = true;
   int expect = -1;
@@ -252,7 +451,13 @@ int main(int argc, char** argv) {
   }
   Trace tr;
   try {
+    const int64_t init_begin = iotrace::now_ns();
+    iotrace::g_paths.store(tr.on && !std::strcmp(std::getenv("AMDKUBE_VADD_TRACE"), "paths"), std::memory_order_relaxed);
+    iotrace::g_window.store(tr.on, std::memory_order_release);
     const hsa_status_t init = hsa_init();
+    iotrace::g_window.store(false, std::memory_order_release);
+    const int64_t init_end = iotrace::now_ns();
+    amdkube::prefetch::cancel();   // nobody reads these files any more (hsa_init may have failed before its /dev/kfd open)
     if (init != HSA_STATUS_SUCCESS) {
       // no /dev/kfd (or no render node) for this container: ROCr cannot open a GPU at all
       const char* msg = nullptr;
@@ -261,6 +466,16 @@ int main(int argc, char** argv) {
       return 2;
     }
     tr.mark("hsa_init");
+    if (tr.on) {
+      iotrace::report(init_begin, init_end);
+      amdkube::prefetch::join();
+      const amdkube::prefetch::Stats ps = amdkube::prefetch::stats();
+      std::fprintf(stderr, "[trace] prefetch %s files=%llu bytes=%llu helper_ms=%.3f hits=%llu misses=%llu distinct=%llu\n",
+                   !prefetch ? "off" : (ps.dropped ? "dropped" : "on"), static_cast<unsigned long long>(ps.files),
+                   static_cast<unsigned long long>(ps.bytes), ps.helper_ms, static_cast<unsigned long long>(ps.hits),
+                   static_cast<unsigned long long>(ps.misses), static_cast<unsigned long long>(ps.distinct));
+      tr.t = std::chrono::steady_clock::now();
+    }
     Agents ag;
     check(hsa_iterate_agents(on_agent, &ag), "iterate agents");
     const int count = static_cast<int>(ag.gpus.size());
@@ -360,8 +575,9 @@ int main(int argc, char** argv) {
       tr.mark("shut down");
     }
     if (json)
-      std::printf("{\"ok\":%s,\"n\":%zu,\"kernel_ms\":%.4f,\"uuid\":\"%s\",\"bus\":\"%s\",\"arch\":\"%s\",\"visible\":%d,\"runtime\":\"hsa\"}\n",
-                  bad ? "false" : "true", n, kernel_ms, id.uuid.c_str(), id.bus.c_str(), id.arch.c_str(), count);
+      std::printf("{\"ok\":%s,\"n\":%zu,\"kernel_ms\":%.4f,\"uuid\":\"%s\",\"bus\":\"%s\",\"arch\":\"%s\",\"visible\":%d,\"runtime\":\"hsa\",\"prefetch\":%s}\n",
+                  bad ? "false" : "true", n, kernel_ms, id.uuid.c_str(), id.bus.c_str(), id.arch.c_str(), count,
+                  prefetch ? "true" : "false");
     if (bad) {
       std::printf("Result verification failed (%zu mismatches)\nTest FAILED\n", bad);
       return 1;
@@ -374,4 +590,17 @@ int main(int argc, char** argv) {
     std::fprintf(stderr, "hsa-vector-add: %s: %s\n", f.what.c_str(), msg ? msg : "error");
     return 4;
   }
+}
+
+}  // namespace
+
+int main(int argc, char** argv) {
+  // first thing, before hsa_init: the helper reads what hsa_init will read while it waits in open("/dev/kfd")
+  bool prefetch = amdkube::prefetch::enabled_by_env();
+  for (int i = 1; i < argc; ++i)
+    if (!std::strcmp(argv[i], "--no-prefetch")) prefetch = false;
+  if (prefetch) amdkube::prefetch::start();
+  const int rc = run(argc, argv, prefetch);
+  amdkube::prefetch::join();   // on every path out of run(), the error returns included
+  return rc;
 }

@@ -33,6 +33,7 @@ int main(int argc, char** argv) {
       return 3;
     }
     amdkube::DevInfo d = amdkube::dev_info(0);
+    if (d.name.empty()) d.name = "AMD Instinct GPU";   // no amdgpu.ids on the host: the same line as hsa-vector-add
     if (print_uuid || !json) std::printf("GPU 0: %s %s bus=%s uuid=%s cus=%d visible=%d\n", d.name.c_str(), d.arch.c_str(),
                                          d.pci_bus_id.c_str(), d.uuid.c_str(), d.cu_count, count);
     std::printf("[Vector addition of %zu elements]\n", n);

@@ -6,10 +6,10 @@
                                     # and the ThreadSanitizer build of the activity sampler
 
 Outputs: amdkube/_native/{_amdsmi,_topo,_kproto,_quantile,_hipops}.<ext> and amdkube/_native/bin/{pause,
-amdkube-nsexec,amdkube-logpump,rocm-vector-add,hsa-vector-add,hbm-probe,gpu-burn,mfma-check,xgmi-probe[,topo-selftest-asan,
+amdkube-nsexec,amdkube-logpump,sysfs-prefetch-selftest,rocm-vector-add,hsa-vector-add,hbm-probe,gpu-burn,mfma-check,xgmi-probe[,topo-selftest-asan,
 pause-asan,
 amdkube-nsexec-asan,amdkube-logpump-asan,
-seccomp-check-asan,sampler-selftest-{asan,tsan}]}.
+seccomp-check-asan,sampler-selftest-{asan,tsan},sysfs-prefetch-selftest-{asan,tsan}]}.
 Targets are rebuilt only when a source/header is newer than the output.
 """
 from __future__ import annotations
@@ -72,6 +72,9 @@ def targets(sanitize=False, cpu_only=False):
          ["g++", "-O2", "-std=c++17", n("native/seccomp_check.cpp"), "-o", "{out}"]),
         (n(BIN, "amdkube-logpump"), [n("native/logpump.cpp")],
          ["g++", "-O2", "-std=c++17", "-Wall", n("native/logpump.cpp"), "-o", "{out}"]),
+        # the KFD-topology prefetch of hsa-vector-add, checked on a fake tree through its own fopen
+        (n(BIN, "sysfs-prefetch-selftest"), [n("native/sysfs_prefetch_selftest.cpp"), n("native/sysfs_prefetch.h")],
+         ["g++", "-O2", "-std=c++17", "-Wall", n("native/sysfs_prefetch_selftest.cpp"), "-pthread", "-ldl", "-o", "{out}"]),
         (n(BIN, "cni", "amdkube-cni"), [n("native/cni_ipam.cpp")],
          ["g++", "-O2", "-std=c++17", n("native/cni_ipam.cpp"), "-o", "{out}"]),
         (n(BIN, "cni", "amdkube-bridge"), [n("native/cni_bridge.cpp")],
@@ -97,6 +100,11 @@ def targets(sanitize=False, cpu_only=False):
              ["g++", "-O1", "-std=c++17", *san, n("native/logpump.cpp"), "-o", "{out}"]),
             (n(BIN, "seccomp-check-asan"), [n("native/seccomp_check.cpp"), n("native/seccomp_bpf.h"), SYSCALL_TABLE],
              ["g++", "-O1", "-std=c++17", *san, n("native/seccomp_check.cpp"), "-o", "{out}"]),
+            (n(BIN, "sysfs-prefetch-selftest-asan"), [n("native/sysfs_prefetch_selftest.cpp"), n("native/sysfs_prefetch.h")],
+             ["g++", "-O1", "-std=c++17", *san, n("native/sysfs_prefetch_selftest.cpp"), "-pthread", "-ldl", "-o", "{out}"]),
+            (n(BIN, "sysfs-prefetch-selftest-tsan"), [n("native/sysfs_prefetch_selftest.cpp"), n("native/sysfs_prefetch.h")],
+             ["g++", "-O1", "-std=c++17", "-fsanitize=thread", "-fno-omit-frame-pointer", "-g",
+              n("native/sysfs_prefetch_selftest.cpp"), "-pthread", "-ldl", "-o", "{out}"]),
             (n(BIN, "sampler-selftest-tsan"), [n("native/sampler_selftest.cpp"), n("native/sampler_core.h")],
              ["g++", "-O1", "-std=c++17", "-fsanitize=thread", "-fno-omit-frame-pointer", "-g",
               n("native/sampler_selftest.cpp"), "-pthread", "-o", "{out}"]),
@@ -114,11 +122,12 @@ def targets(sanitize=False, cpu_only=False):
              [*ho, "-shared", "-fPIC", *py, n("native/hipops.hip"), "-o", "{out}"]),
             (n(BIN, "rocm-vector-add"), [n("kernels/vector_add.hip"), hdr], [*ho, n("kernels/vector_add.hip"), "-o", "{out}"]),
             # the HIP-free pod workload: a bare gfx950 code object, then the HSA host embedding it
-            (n(BIN, "hsa-vector-add"), [n("kernels/hsa_vector_add.cpp"), n("kernels/vadd_kernel.hip")],
+            (n(BIN, "hsa-vector-add"), [n("kernels/hsa_vector_add.cpp"), n("kernels/vadd_kernel.hip"),
+                                        n("native/sysfs_prefetch.h")],
              ["sh", "-c", f'"$0" --offload-arch={ARCH} -O3 --offload-device-only --no-gpu-bundle-output -c '
               f'{n("kernels/vadd_kernel.hip")} -o {n(OUT, "lib", "vadd_" + ARCH + ".co")} && '
               f'g++ -O2 -std=c++17 -Wall -DVADD_CO_PATH=\\"{n(OUT, "lib", "vadd_" + ARCH + ".co")}\\" '
-              f'-I{ROCM}/include {n("kernels/hsa_vector_add.cpp")} -L{ROCM}/lib -Wl,-rpath,{ROCM}/lib -lhsa-runtime64 -o "$1"',
+              f'-I{ROCM}/include {n("kernels/hsa_vector_add.cpp")} -L{ROCM}/lib -Wl,-rpath,{ROCM}/lib -lhsa-runtime64 -pthread -ldl -o "$1"',
               hip, "{out}"]),
             (n(BIN, "hbm-probe"), [n("kernels/hbm_probe.hip"), hdr], [*ho, n("kernels/hbm_probe.hip"), "-o", "{out}"]),
             (n(BIN, "gpu-burn"), [n("kernels/gpu_burn.hip"), hdr, chk, lp], [*ho, n("kernels/gpu_burn.hip"), "-o", "{out}"]),
