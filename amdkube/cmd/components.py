@@ -895,7 +895,8 @@ def device_plugin_parser():
         return spec
     ap.add_argument("--health-probe", default="none", type=health_probe, metavar="LIST",
                     help="on-device checks before a GPU is advertised: none, or a comma list over hbm (HBM pattern "
-                         "probe), mfma (bf16 matrix-core check) and mfma-lp (FP8 / MXFP8 / MXFP4 matrix-core check)")
+                         "probe), mfma (bf16 matrix-core check), mfma-lp (FP8 / MXFP8 / MXFP4 matrix-core check) and cu "
+                         "(per-CU check: LDS march, vector ALU pipes, transcendental unit, with the CU of each error)")
     ap.add_argument("--max-gpus", type=int, default=None, help="advertise only the first N physical GPUs")
     ap.add_argument("--resource-naming", default="single", choices=("single", "mixed"),
                     help="partitioned GPUs: single=amd.com/gpu for all, mixed=amd.com/<cpx>_<nps> per partition type")

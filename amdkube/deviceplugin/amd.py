@@ -145,16 +145,30 @@ HEALTH_PROBES = {
 }
 
 
+# The per-CU check runs after them: the whole LDS, the vector ALU pipes and the transcendental unit of
+# every CU, with the XCD / shader engine / CU of each error. Without --require-coverage: a GPU does not
+# go Unhealthy on a placement the dispatcher does not promise.
+HEALTH_PROBES_CU = {
+    "cu": ("cu-check", ["--ms", "200"]),
+}
+
+
+def all_health_probes() -> dict:
+    """Every probe in run order: HEALTH_PROBES, then HEALTH_PROBES_CU."""
+    return {**HEALTH_PROBES, **HEALTH_PROBES_CU}
+
+
 def parse_health_probe(spec: str) -> list[str]:
-    """`none`, or a comma list over HEALTH_PROBES → the probes to run, HBM first."""
+    """`none`, or a comma list over all_health_probes() → the probes to run, HBM first."""
+    known = all_health_probes()
     names = [p.strip() for p in str(spec).split(",")]
     if names == ["none"]:
         return []
-    bad = [p for p in names if p not in HEALTH_PROBES]
+    bad = [p for p in names if p not in known]
     if bad:
         raise ValueError(f"unknown health probe {bad[0]!r} in {spec!r}: expected none or a comma list of "
-                         f"{', '.join(HEALTH_PROBES)}")
-    return [p for p in HEALTH_PROBES if p in names]
+                         f"{', '.join(known)}")
+    return [p for p in known if p in names]
 
 
 class AMDGPUPlugin(DevicePluginServer):
@@ -269,14 +283,15 @@ class AMDGPUPlugin(DevicePluginServer):
                 log.error("health check failed: %s", e)
 
     async def _probe_all(self):
-        """Run the configured on-device probes (HBM pattern, matrix-core checks) on each GPU
+        """Run the configured on-device probes (HBM pattern, matrix-core checks, per-CU check) on each GPU
         (subprocess → isolated HIP context); the first failure takes the GPU out of service."""
+        known = all_health_probes()
         for g in self.gpus:
             did = device_id(g)
             env = {k: v for k, v in os.environ.items() if k not in ("HIP_VISIBLE_DEVICES", "CUDA_VISIBLE_DEVICES")}
             env["ROCR_VISIBLE_DEVICES"] = visibility_token(g)
             for probe in self.probes:
-                name, args = HEALTH_PROBES[probe]
+                name, args = known[probe]
                 try:
                     r = await asyncio.to_thread(subprocess.run, [os.path.join(BIN_DIR, name), *args], env=env,
                                                 capture_output=True, text=True, timeout=60)

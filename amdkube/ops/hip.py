@@ -177,6 +177,48 @@ def mfma_check_tile(block: int, seed: int = 0x5EED, device: int = 0, dtype: str 
     return tuple(torch.from_numpy(np.asarray(x).copy()) for x in t)
 
 
+def cu_check(rounds: int | None = None, ms: float = 50.0, device: int = 0, seed: int = 0x5EED,
+             selftest_flips: int = 0, units=("lds", "valu", "trans")) -> dict:
+    """The per-CU integrity check (cu-check in process, kernels/cu_check.h): every workgroup owns a
+    whole CU's LDS, marches all 160 KiB of it (`lds`), compares the same multiply-adds on the fp32,
+    packed-fp32, fp64 and integer pipes (`valu`) and the transcendental unit on two waves (`trans`),
+    and says where it ran. `rounds` runs exactly that many, otherwise the run is calibrated to ~`ms`.
+    `selftest_flips` perturbs that many compared values, which the check must then report. The
+    result carries the coverage (`cus`, `cus_covered`, `xccs`, `locations`, and `block_loc`, the raw
+    location words of every workgroup of the timed launch), `errors_by_unit`, `bad_cus` and records
+    with `unit`, `block`, `xcc`, `se`, `sh`, `cu`, `round`, `pass`, `index`, `got` and `want`. While
+    places are missing, up to 3 further launches of one round are added (`launches`)."""
+    from . import cucheck
+    mask = cucheck.units_mask(units)
+    if rounds is not None and rounds < 1:
+        raise ValueError("rounds must be at least 1")
+    if not 0 <= int(selftest_flips) <= cucheck.MAX_FLIPS:
+        raise ValueError(f"selftest_flips must be in [0, {cucheck.MAX_FLIPS}]")
+    r = dict(_need().cu_check(int(rounds or 0), float(ms), device, seed, int(selftest_flips), mask))
+    for k in ("first_errors", "bad_cus", "locations"):
+        r[k] = [dict(e) for e in r[k]]
+    r["errors_by_unit"] = dict(r["errors_by_unit"])
+    r["units"] = list(r["units"])
+    return r
+
+
+def cu_check_dump(block: int, seed: int = 0x5EED, device: int = 0) -> dict:
+    """What workgroup `block` of a one-round check wrote and computed, as numpy arrays: `lds` (the
+    40,960 words read back after pass 1), `valu_ops`, `valu_f32`, `valu_f64`, `valu_int`, `trans_in`,
+    `trans_out` (layouts: amdkube.ops.cucheck), with the raw `hw_id` / `xcc_id` words and the decoded
+    `location` of the workgroup."""
+    import numpy as np
+    from . import cucheck
+    if block < 0:
+        raise ValueError("block must not be negative")
+    d = dict(_need().cu_check_dump(int(block), seed, device))
+    for k, v in d.items():
+        if k not in ("hw_id", "xcc_id"):
+            d[k] = np.asarray(v).copy()
+    d["location"] = cucheck.decode_location(d["hw_id"], d["xcc_id"])
+    return d
+
+
 def hbm_pattern(n16: int, seed: int = 0x5EED, device: int = 0):
     """The HBM probe's write pattern for n16 16-byte words, as uint32 words."""
     import numpy as np

@@ -56,6 +56,7 @@ def builtin_images() -> dict[str, dict]:
         "amdkube/hbm-probe:latest": {"entrypoint": [_b("hbm-probe")]},
         "amdkube/gpu-burn:latest": {"entrypoint": [_b("gpu-burn")]},
         "amdkube/mfma-check:latest": {"entrypoint": [_b("mfma-check")]},
+        "amdkube/cu-check:latest": {"entrypoint": [_b("cu-check")]},
         "amdkube/xgmi-probe:latest": {"entrypoint": [_b("xgmi-probe")]},
         "busybox:latest": {"entrypoint": [sh]},
         "python:3": {"entrypoint": [py]},

@@ -3,8 +3,8 @@
 // The reference's only GPU workload is the CUDA-samples vectorAdd image its e2e tests run
 // in GPU pods (test/images/cuda-vector-add/Dockerfile:15-26; 50,000 fp32 elements), plus
 // device health that comes solely from the plugin (api.proto:97). amdkube replaces that
-// with four CDNA4-native kernels shared by the standalone pod binaries (rocm-vector-add,
-// hbm-probe, gpu-burn, mfma-check) and the in-process Python extension (_hipops):
+// with five CDNA4-native kernels shared by the standalone pod binaries (rocm-vector-add,
+// hbm-probe, gpu-burn, mfma-check, cu-check) and the in-process Python extension (_hipops):
 //
 //   vector add   wave64 grid-stride, 16-B (float4) loads, grid sized to the chip
 //   HBM probe    address-hashed write / verify / read / copy over buffers larger than
@@ -16,6 +16,9 @@
 //   MFMA check   (mfma_check.h) LDS-staged 64x64 bf16 tiles whose every result is compared:
 //                round 0 with exact int32 arithmetic, later rounds bitwise with round 0;
 //                (mfma_check_lp.h) the same on the FP8 MFMA and the block-scaled MXFP8 / MXFP4 forms
+//   CU check     (cu_check.h) one workgroup per CU with all 160 KiB of LDS: a march over the LDS, the
+//                same multiply-adds on the fp32, packed-fp32, fp64 and integer pipes, the
+//                transcendental unit on two waves, and the XCD / shader engine / CU it ran on
 //
 // Every launch is bounded by construction (grid-stride loops over checked sizes) and uses
 // no inter-workgroup synchronisation, so no launch can hang the device.
@@ -552,3 +555,4 @@ inline BurnResult run_mfma_burn(double target_ms, int dev) {
 
 #include "mfma_check.h"  // the checked matrix-core workload: mfma_gemm_kernel, mfma_check_kernel, their runners
 #include "mfma_check_lp.h"  // the same for the FP8, MXFP8 and MXFP4 matrix-core paths
+#include "cu_check.h"  // the per-CU check: LDS march, vector ALU and transcendental cross-checks, workgroup placement

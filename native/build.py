@@ -6,7 +6,7 @@
                                     # and the ThreadSanitizer build of the activity sampler
 
 Outputs: amdkube/_native/{_amdsmi,_topo,_kproto,_quantile,_hipops}.<ext> and amdkube/_native/bin/{pause,
-amdkube-nsexec,amdkube-logpump,sysfs-prefetch-selftest,rocm-vector-add,hsa-vector-add,hbm-probe,gpu-burn,mfma-check,xgmi-probe[,topo-selftest-asan,
+amdkube-nsexec,amdkube-logpump,sysfs-prefetch-selftest,rocm-vector-add,hsa-vector-add,hbm-probe,gpu-burn,mfma-check,cu-check,xgmi-probe[,topo-selftest-asan,
 pause-asan,
 amdkube-nsexec-asan,amdkube-logpump-asan,
 seccomp-check-asan,sampler-selftest-{asan,tsan},sysfs-prefetch-selftest-{asan,tsan}]}.
@@ -117,10 +117,11 @@ def targets(sanitize=False, cpu_only=False):
         hdr = n("kernels/gpu_common.h")
         chk = n("kernels/mfma_check.h")      # included by gpu_common.h
         lp = n("kernels/mfma_check_lp.h")    # included by gpu_common.h
+        cu = n("kernels/cu_check.h")         # included by gpu_common.h
         t += [
-            (n(OUT, "_hipops" + EXT), [n("native/hipops.hip"), hdr, chk, lp],
+            (n(OUT, "_hipops" + EXT), [n("native/hipops.hip"), hdr, chk, lp, cu],
              [*ho, "-shared", "-fPIC", *py, n("native/hipops.hip"), "-o", "{out}"]),
-            (n(BIN, "rocm-vector-add"), [n("kernels/vector_add.hip"), hdr], [*ho, n("kernels/vector_add.hip"), "-o", "{out}"]),
+            (n(BIN, "rocm-vector-add"), [n("kernels/vector_add.hip"), hdr, chk, lp, cu], [*ho, n("kernels/vector_add.hip"), "-o", "{out}"]),
             # the HIP-free pod workload: a bare gfx950 code object, then the HSA host embedding it
             (n(BIN, "hsa-vector-add"), [n("kernels/hsa_vector_add.cpp"), n("kernels/vadd_kernel.hip"),
                                         n("native/sysfs_prefetch.h")],
@@ -129,10 +130,12 @@ def targets(sanitize=False, cpu_only=False):
               f'g++ -O2 -std=c++17 -Wall -DVADD_CO_PATH=\\"{n(OUT, "lib", "vadd_" + ARCH + ".co")}\\" '
               f'-I{ROCM}/include {n("kernels/hsa_vector_add.cpp")} -L{ROCM}/lib -Wl,-rpath,{ROCM}/lib -lhsa-runtime64 -pthread -ldl -o "$1"',
               hip, "{out}"]),
-            (n(BIN, "hbm-probe"), [n("kernels/hbm_probe.hip"), hdr], [*ho, n("kernels/hbm_probe.hip"), "-o", "{out}"]),
-            (n(BIN, "gpu-burn"), [n("kernels/gpu_burn.hip"), hdr, chk, lp], [*ho, n("kernels/gpu_burn.hip"), "-o", "{out}"]),
-            (n(BIN, "mfma-check"), [n("kernels/mfma_check.hip"), hdr, chk, lp],
+            (n(BIN, "hbm-probe"), [n("kernels/hbm_probe.hip"), hdr, chk, lp, cu], [*ho, n("kernels/hbm_probe.hip"), "-o", "{out}"]),
+            (n(BIN, "gpu-burn"), [n("kernels/gpu_burn.hip"), hdr, chk, lp, cu], [*ho, n("kernels/gpu_burn.hip"), "-o", "{out}"]),
+            (n(BIN, "mfma-check"), [n("kernels/mfma_check.hip"), hdr, chk, lp, cu],
              [*ho, n("kernels/mfma_check.hip"), "-o", "{out}"]),
+            (n(BIN, "cu-check"), [n("kernels/cu_check.hip"), hdr, chk, lp, cu],
+             [*ho, n("kernels/cu_check.hip"), "-o", "{out}"]),
             (n(BIN, "xgmi-probe"), [n("kernels/xgmi_probe.cpp")],
              [*ho, "-x", "hip", n("kernels/xgmi_probe.cpp"), *rocm_inc, *rpath, "-lrccl", "-o", "{out}"]),
         ]

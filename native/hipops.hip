@@ -36,11 +36,68 @@ static py::dict check_result(const amdkube::MfmaCheckResult& r, const char* rate
   return o;
 }
 
+static const char* const kCuUnits[3] = {"lds", "valu", "trans"};
+
+static py::dict cu_location(const amdkube::CuLocation& l) {
+  py::dict d;
+  d["xcc"] = l.xcc;
+  d["se"] = l.se;
+  d["sh"] = l.sh;
+  d["cu"] = l.cu;
+  return d;
+}
+
+// the result of a per-CU check run (kernels/cu_check.h)
+static py::dict cu_check_result(const amdkube::CuCheckResult& r) {
+  py::dict o, by_unit;
+  py::list units, locations, bad, recs;
+  for (int u = 0; u < 3; ++u) {
+    if (r.units & (1 << u)) units.append(kCuUnits[u]);
+    by_unit[kCuUnits[u]] = r.errors_by_unit[u];
+  }
+  for (const amdkube::CuLocation& l : r.locations) locations.append(cu_location(l));
+  for (const amdkube::CuCheckBadCu& b : r.bad_cus) {
+    py::dict d = cu_location(b.where);
+    d["errors"] = b.errors;
+    bad.append(d);
+  }
+  for (const amdkube::CuCheckRecord& e : r.first_errors) {
+    py::dict d = cu_location(amdkube::cu_decode_location(e.hw_id, e.xcc_id));
+    d["unit"] = kCuUnits[e.unit < 3 ? e.unit : 0];
+    d["block"] = e.block;
+    d["round"] = e.round;
+    d["pass"] = e.pass;
+    d["index"] = e.index;
+    d["got"] = e.got;
+    d["want"] = e.want;
+    recs.append(d);
+  }
+  o["ok"] = r.errors == 0;
+  o["errors"] = r.errors;
+  o["errors_by_unit"] = by_unit;
+  o["units"] = units;
+  o["rounds"] = r.rounds;
+  o["blocks"] = r.blocks;
+  o["launches"] = r.launches;
+  o["ms"] = r.ms;
+  o["lds_gbps"] = r.lds_gbps;
+  o["valu_gops"] = r.valu_gops;
+  o["cus"] = r.cus;
+  o["cus_covered"] = r.cus_covered;
+  o["xccs"] = r.xccs;
+  o["locations"] = locations;
+  // raw HW_ID and XCC_ID words of every workgroup of the timed launch
+  o["block_loc"] = py::array_t<uint32_t>({static_cast<py::ssize_t>(r.blocks), static_cast<py::ssize_t>(2)}, r.block_loc.data());
+  o["bad_cus"] = bad;
+  o["first_errors"] = recs;
+  return o;
+}
+
 using bytes_in = py::array_t<uint8_t, py::array::c_style | py::array::forcecast>;
 static std::vector<uint8_t> to_vec(const bytes_in& x) { return std::vector<uint8_t>(x.data(), x.data() + x.size()); }
 
 PYBIND11_MODULE(_hipops, m) {
-  m.doc() = "amdkube HIP (gfx950) validation kernels: vector add, HBM probe, MFMA burn, MFMA check";
+  m.doc() = "amdkube HIP (gfx950) validation kernels: vector add, HBM probe, MFMA burn, MFMA check, CU check";
   m.def("device_count", []() {
     int n = 0;
     AK_HIP(hipGetDeviceCount(&n));
@@ -234,6 +291,43 @@ PYBIND11_MODULE(_hipops, m) {
                               py::array_t<float>({amdkube::MFMA_TILE, amdkube::MFMA_TILE}, t.c.data()));
       },
       py::arg("dtype"), py::arg("block"), py::arg("seed") = 0x5eedu, py::arg("device") = 0);
+  // the per-CU check (kernels/cu_check.h): units is a mask over lds = 1, valu = 2, trans = 4
+  m.def(
+      "cu_check",
+      [](int rounds, double ms, int dev, uint32_t seed, int flips, int units) {
+        amdkube::CuCheckResult r;
+        {
+          py::gil_scoped_release nogil;
+          r = amdkube::run_cu_check(rounds, ms, dev, seed, flips, units);
+        }
+        return cu_check_result(r);
+      },
+      py::arg("rounds") = 0, py::arg("ms") = 50.0, py::arg("device") = 0, py::arg("seed") = 0x5eedu,
+      py::arg("selftest_flips") = 0, py::arg("units") = 7);
+  m.def(
+      "cu_check_dump",
+      [](int block, uint32_t seed, int dev) {
+        amdkube::CuCheckDump d;
+        {
+          py::gil_scoped_release nogil;
+          d = amdkube::cu_check_dump_host(block, seed, dev);
+        }
+        const py::ssize_t T = amdkube::CU_CHECK_THREADS;
+        py::dict o;
+        o["hw_id"] = d.hw_id;
+        o["xcc_id"] = d.xcc_id;
+        o["lds"] = py::array_t<uint32_t>(d.lds.size(), d.lds.data());
+        o["valu_ops"] = py::array_t<uint32_t>({T, static_cast<py::ssize_t>(amdkube::CU_CHECK_VALU_OPS)}, d.valu_ops.data());
+        o["valu_f32"] = py::array_t<float>({T, static_cast<py::ssize_t>(4)}, d.valu_f32.data());
+        o["valu_f64"] = py::array_t<double>({T, static_cast<py::ssize_t>(3)}, d.valu_f64.data());
+        o["valu_int"] = py::array_t<uint64_t>({T, static_cast<py::ssize_t>(4)},
+                                              reinterpret_cast<const uint64_t*>(d.valu_int.data()));
+        const std::vector<py::ssize_t> ts = {T, amdkube::CU_CHECK_TRANS_FUNCS, amdkube::CU_CHECK_TRANS_SETS};
+        o["trans_in"] = py::array_t<float>(ts, d.trans_in.data());
+        o["trans_out"] = py::array_t<float>(ts, d.trans_out.data());
+        return o;
+      },
+      py::arg("block"), py::arg("seed") = 0x5eedu, py::arg("device") = 0);
   m.def(
       "mfma_burn",
       [](double ms, int dev) {
