@@ -40,7 +40,7 @@ def mix32(x):
 
 
 def key(seed: int, block: int, tag):
-    """mix32(seed, block, tag) of kernels/mfma_check.h, as uint64 holding 32-bit values."""
+    """mix32(seed, block, tag) of kernels/gpu_common.h, as uint64 holding 32-bit values."""
     s = mix32((int(seed) ^ (0x9E3779B9 * (int(block) + 1))) & 0xFFFFFFFF)
     return mix32((s + np.asarray(tag, dtype=np.uint64)) & _M32)
 

@@ -1,7 +1,7 @@
 // Per-CU integrity check: an LDS march over the whole 160 KiB, a cross-check of the vector ALU
 // pipes, an agreement check of the transcendental unit, and the physical place of every workgroup.
-// Behind cu-check, the device plugin's cu health probe and hip.cu_check. Included by gpu_common.h
-// after mfma_check_lp.h, which provide mix32 (one- and three-argument), v4u, AK_HIP and DevBuf.
+// Behind cu-check, the device plugin's cu health probe and hip.cu_check. gpu_common.h provides
+// mix32 (one- and three-argument), v4u and the host plumbing.
 //
 // A workgroup of cu_check_kernel declares all 163,840 B of LDS, so it has its CU to itself: one
 // workgroup is one CU for its lifetime, and the location wave 0 reads at entry is the location of
@@ -11,7 +11,7 @@
 // errors are one atomicAdd per lane that saw a mismatch and at most 16 records are kept.
 //
 // Formulas (amdkube/ops/cucheck.py is written from these, not from the device):
-//   key(tag)     = mix32(seed, block, tag), the three-argument mix32 of mfma_check.h
+//   key(tag)     = mix32(seed, block, tag), the three-argument mix32 of gpu_common.h
 //   lds          word address wa in [0, 40960) (byte address 4 wa), round r:
 //                k = key(0x4c000000 + r), mul = k | 1, add = mix32(k ^ 0x85ebca6b),
 //                P(wa) = wa * mul + add (mod 2^32; mul is odd, so P is a bijection of wa).
@@ -50,6 +50,8 @@
 
 #include <map>
 #include <set>
+
+#include "gpu_common.h"
 
 namespace amdkube {
 
@@ -478,18 +480,17 @@ inline CuLocation cu_decode_location(uint32_t hw_id, uint32_t xcc_id) {
 
 inline int cu_check_blocks(int cu_count) { return (cu_count > 0 ? cu_count : 256) * CU_CHECK_BLOCKS_PER_CU; }
 
+// unit u has the mask bit 1 << u and the number u in a record
+constexpr const char* CU_UNIT_NAMES[3] = {"lds", "valu", "trans"};
+
 // "lds,valu,trans" -> mask; throws std::invalid_argument on an unknown or empty name
 inline int cu_check_units(const std::string& list) {
   int mask = 0;
-  for (size_t at = 0; at <= list.size();) {
-    size_t end = list.find(',', at);
-    if (end == std::string::npos) end = list.size();
-    const std::string name = list.substr(at, end - at);
-    if (name == "lds") mask |= CU_UNIT_LDS;
-    else if (name == "valu") mask |= CU_UNIT_VALU;
-    else if (name == "trans") mask |= CU_UNIT_TRANS;
-    else throw std::invalid_argument("unknown unit '" + name + "': expected a comma list over lds, valu, trans");
-    at = end + 1;
+  for (const std::string& name : split_list(list)) {
+    int u = 0;
+    while (u < 3 && name != CU_UNIT_NAMES[u]) ++u;
+    if (u == 3) throw std::invalid_argument("unknown unit '" + name + "': expected a comma list over lds, valu, trans");
+    mask |= 1 << u;
   }
   return mask;
 }
@@ -514,7 +515,7 @@ struct CuCheckResult {
 // Device buffers and the launch of one check; errors and records accumulate over launches, the
 // places and per-workgroup error counts are collected after each launch.
 struct CuCheckRun {
-  int blocks, units, cus;
+  int cus, blocks, units;
   uint32_t seed;
   DevBuf errors, block_errors, nrec, recs, flip_pos, loc;
   std::set<uint32_t> seen;
@@ -522,44 +523,31 @@ struct CuCheckRun {
   std::vector<uint32_t> block_loc;
   int launches = 0;
   CuCheckRun(int dev, uint32_t seed_, int units_)
-      : blocks(cu_check_blocks(dev_info(dev).cu_count)), units(units_), cus(dev_info(dev).cu_count), seed(seed_),
-        errors(3 * sizeof(unsigned long long)), block_errors(blocks * sizeof(unsigned)), nrec(sizeof(unsigned)),
-        recs(CU_CHECK_RECORDS * sizeof(CuCheckRecord)), flip_pos(CU_CHECK_MAX_FLIPS * sizeof(uint32_t)),
-        loc(blocks * 2 * sizeof(uint32_t)), block_loc(static_cast<size_t>(blocks) * 2) {
-    if (units < 1 || units > CU_UNIT_ALL) throw std::invalid_argument("units must name at least one of lds, valu, trans");
+      : cus(dev_info(dev).cu_count), blocks(cu_check_blocks(cus)), units(checked_units(units_)), seed(seed_),
+        errors(3 * sizeof(unsigned long long), DevBuf::zeroed), block_errors(blocks * sizeof(unsigned), DevBuf::zeroed),
+        nrec(sizeof(unsigned), DevBuf::zeroed), recs(CU_CHECK_RECORDS * sizeof(CuCheckRecord), DevBuf::zeroed),
+        flip_pos(flip_table(seed_, blocks, units)), loc(blocks * 2 * sizeof(uint32_t), DevBuf::zeroed),
+        block_loc(static_cast<size_t>(blocks) * 2) {
     hipDeviceProp_t p;
     AK_HIP(hipGetDeviceProperties(&p, dev));
     if (p.sharedMemPerBlock < static_cast<size_t>(CU_CHECK_LDS_BYTES))
       throw std::runtime_error("cu-check needs 163840 bytes of LDS per workgroup, the device offers " +
                                std::to_string(p.sharedMemPerBlock));
-    AK_HIP(hipMemset(errors.p, 0, 3 * sizeof(unsigned long long)));
-    AK_HIP(hipMemset(block_errors.p, 0, blocks * sizeof(unsigned)));
-    AK_HIP(hipMemset(nrec.p, 0, sizeof(unsigned)));
-    AK_HIP(hipMemset(recs.p, 0, CU_CHECK_RECORDS * sizeof(CuCheckRecord)));
-    AK_HIP(hipMemset(loc.p, 0, blocks * 2 * sizeof(uint32_t)));
-    // Flip i belongs to unit slot i mod n_en; its position is (base + i * stride) mod (blocks * elems) of
-    // that unit, elems = 40960 words (lds) or 1024 lanes (valu, trans). The stride is coprime to
-    // both moduli, so the positions of one unit are distinct.
+  }
+  static int checked_units(int units) {
+    if (units < 1 || units > CU_UNIT_ALL) throw std::invalid_argument("units must name at least one of lds, valu, trans");
+    return units;
+  }
+  // Flip i belongs to unit slot i mod n_en; its position is (base + i * stride) mod (blocks * elems) of
+  // that unit, elems = 40960 words (lds) or 1024 lanes (valu, trans). The stride is coprime to
+  // both moduli (the smaller divides the larger), so the positions of one unit are distinct.
+  static std::vector<uint32_t> flip_table(uint32_t seed, int blocks, int units) {
     const unsigned long long small = static_cast<unsigned long long>(blocks) * CU_CHECK_THREADS;
     const unsigned long long large = static_cast<unsigned long long>(blocks) * CU_CHECK_WORDS;
-    auto gcd = [](unsigned long long a, unsigned long long b) {
-      while (b) {
-        const unsigned long long r = a % b;
-        a = b;
-        b = r;
-      }
-      return a;
-    };
-    const unsigned long long base = seed * 2654435761ull + 0x5bd1e995u;
-    unsigned long long stride = (((seed ^ 0x9e3779b9u) * 0x85ebca6bull) % small) | 1;
-    while (gcd(stride, large) != 1) stride += 2;  // small divides large
-    int slot_unit[3], n_en = 0;
+    std::vector<unsigned long long> slot_mod;
     for (int u = 0; u < 3; ++u)
-      if (units & (1 << u)) slot_unit[n_en++] = u;
-    std::vector<uint32_t> pos(CU_CHECK_MAX_FLIPS);
-    for (size_t i = 0; i < pos.size(); ++i)
-      pos[i] = static_cast<uint32_t>((base + i * stride) % (slot_unit[i % n_en] == 0 ? large : small));
-    AK_HIP(hipMemcpy(flip_pos.p, pos.data(), pos.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
+      if (units & (1 << u)) slot_mod.push_back(u == 0 ? large : small);
+    return flip_positions(seed, CU_CHECK_MAX_FLIPS, small, large, slot_mod);
   }
   CuCheckArgs args(int rounds, int flips) const {
     CuCheckArgs a = {};
@@ -568,12 +556,12 @@ struct CuCheckRun {
     a.flips = flips;
     a.units = units;
     a.dbg_block = -1;
-    a.flip_pos = static_cast<const uint32_t*>(flip_pos.p);
-    a.errors = static_cast<unsigned long long*>(errors.p);
-    a.block_errors = static_cast<unsigned*>(block_errors.p);
-    a.nrec = static_cast<unsigned*>(nrec.p);
-    a.recs = static_cast<CuCheckRecord*>(recs.p);
-    a.loc = static_cast<uint32_t*>(loc.p);
+    a.flip_pos = flip_pos.as<const uint32_t>();
+    a.errors = errors.as<unsigned long long>();
+    a.block_errors = block_errors.as<unsigned>();
+    a.nrec = nrec.as<unsigned>();
+    a.recs = recs.as<CuCheckRecord>();
+    a.loc = loc.as<uint32_t>();
     return a;
   }
   void launch(const CuCheckArgs& a) {
@@ -583,9 +571,8 @@ struct CuCheckRun {
   }
   // after a finished launch: where its workgroups ran, and which of them counted errors
   void collect() {
-    std::vector<unsigned> be(blocks);
-    AK_HIP(hipMemcpy(block_loc.data(), loc.p, block_loc.size() * sizeof(uint32_t), hipMemcpyDeviceToHost));
-    AK_HIP(hipMemcpy(be.data(), block_errors.p, be.size() * sizeof(unsigned), hipMemcpyDeviceToHost));
+    block_loc = loc.download<uint32_t>();
+    const std::vector<unsigned> be = block_errors.download<unsigned>();
     bool any = false;
     for (int b = 0; b < blocks; ++b) {
       const uint32_t key = cu_decode_location(block_loc[2 * b], block_loc[2 * b + 1]).key();
@@ -595,7 +582,7 @@ struct CuCheckRun {
         any = true;
       }
     }
-    if (any) AK_HIP(hipMemset(block_errors.p, 0, blocks * sizeof(unsigned)));
+    if (any) block_errors.zero();
   }
 };
 
@@ -608,51 +595,24 @@ inline CuLocation cu_location_of_key(uint32_t key) {
   return l;
 }
 
-// rounds > 0: one launch of exactly that many rounds. rounds <= 0: calibrate to ~target_ms by
-// mfma_check_drive's scheme (the self-test flips then go into the last launch only).
+// rounds > 0: one launch of exactly that many rounds. rounds <= 0: calibrated to ~target_ms
+// (check_core.h; the self-test flips go into the last launch only).
 inline CuCheckResult cu_check_drive(CuCheckRun& run, int rounds, double target_ms, int flips) {
-  hipEvent_t e0, e1;
-  AK_HIP(hipEventCreate(&e0));
-  AK_HIP(hipEventCreate(&e1));
-  auto timed = [&](int r, int f) {
-    AK_HIP(hipEventRecord(e0));
-    run.launch(run.args(r, f));
-    AK_HIP(hipEventRecord(e1));
-    AK_HIP(hipEventSynchronize(e1));
-    float ms = 0;
-    AK_HIP(hipEventElapsedTime(&ms, e0, e1));
-    run.collect();
-    return static_cast<double>(ms);
-  };
-  double ms;
-  if (rounds > 0) {
-    ms = timed(rounds, flips);
-  } else {
-    rounds = 16;
-    ms = timed(rounds, 0);  // warm-up: code-object load and clock ramp inflate the first launch
-    while (ms < 20.0 && rounds < (1 << 26)) {
-      rounds *= 4;
-      ms = timed(rounds, 0);
-    }
-    const bool longer = target_ms > ms && ms > 0;
-    if (longer) {
-      const double want = rounds * (target_ms / ms);
-      rounds = want > 2.0e9 ? 2000000000 : static_cast<int>(want);
-    }
-    if (longer || flips > 0) ms = timed(rounds, flips);
-  }
-  hipEventDestroy(e0);
-  hipEventDestroy(e1);
+  GpuTimer timer;
+  const Calibrated c = calibrate(
+      [&](int r, int f) {
+        const double ms = timer.time([&] { run.launch(run.args(r, f)); });
+        run.collect();
+        return ms;
+      },
+      16, 1 << 26, rounds, target_ms, flips);
   CuCheckResult r;
-  unsigned n = 0;
-  AK_HIP(hipMemcpy(r.errors_by_unit, run.errors.p, sizeof(r.errors_by_unit), hipMemcpyDeviceToHost));
-  AK_HIP(hipMemcpy(&n, run.nrec.p, sizeof(n), hipMemcpyDeviceToHost));
-  r.first_errors.resize(n < static_cast<unsigned>(CU_CHECK_RECORDS) ? n : CU_CHECK_RECORDS);
-  if (!r.first_errors.empty())
-    AK_HIP(hipMemcpy(r.first_errors.data(), run.recs.p, r.first_errors.size() * sizeof(CuCheckRecord), hipMemcpyDeviceToHost));
+  const std::vector<unsigned long long> by_unit = run.errors.download<unsigned long long>();
+  for (int u = 0; u < 3; ++u) r.errors_by_unit[u] = by_unit[u];
+  r.first_errors = fetch_records<CuCheckRecord>(run.nrec, run.recs);
   r.errors = r.errors_by_unit[0] + r.errors_by_unit[1] + r.errors_by_unit[2];
-  r.ms = ms;
-  r.rounds = rounds;
+  r.ms = c.ms;
+  r.rounds = c.rounds;
   r.blocks = run.blocks;
   r.units = run.units;
   r.launches = run.launches;
@@ -670,7 +630,7 @@ inline CuCheckResult cu_check_drive(CuCheckRun& run, int rounds, double target_m
     r.bad_cus.push_back(CuCheckBadCu{cu_location_of_key(kv.first), kv.second});
   }
   // rates of the last launch over its whole time: a unit's own rate when it runs alone
-  const double per_s = static_cast<double>(run.blocks) * rounds / (ms * 1e-3);
+  const double per_s = static_cast<double>(run.blocks) * c.rounds / (c.ms * 1e-3);
   if (run.units & CU_UNIT_LDS) r.lds_gbps = per_s * 6.0 * CU_CHECK_LDS_BYTES / 1e9;  // three store and three load passes
   if (run.units & CU_UNIT_VALU) r.valu_gops = per_s * CU_CHECK_THREADS * CU_CHECK_VALU_MADS / 1e9;
   return r;
@@ -710,37 +670,30 @@ inline CuCheckDump cu_check_dump_host(int block, uint32_t seed, int dev) {
   CuCheckRun run(dev, seed, CU_UNIT_ALL);
   if (block < 0 || block >= run.blocks) throw std::invalid_argument("block out of range");
   const size_t T = CU_CHECK_THREADS;
-  CuCheckDump d;
-  d.lds.resize(CU_CHECK_WORDS);
-  d.valu_ops.resize(T * CU_CHECK_VALU_OPS);
-  d.valu_f32.resize(T * 4);
-  d.valu_f64.resize(T * 3);
-  d.valu_int.resize(T * 4);
-  d.trans_in.resize(T * CU_CHECK_TRANS_N);
-  d.trans_out.resize(T * CU_CHECK_TRANS_N);
-  DevBuf lds(d.lds.size() * 4), ops(d.valu_ops.size() * 4), f32(d.valu_f32.size() * 4), f64(d.valu_f64.size() * 8),
-      i64(d.valu_int.size() * 8), tin(d.trans_in.size() * 4), tout(d.trans_out.size() * 4);
+  DevBuf lds(CU_CHECK_WORDS * 4), ops(T * CU_CHECK_VALU_OPS * 4), f32(T * 4 * 4), f64(T * 3 * 8), i64(T * 4 * 8),
+      tin(T * CU_CHECK_TRANS_N * 4), tout(T * CU_CHECK_TRANS_N * 4);
   CuCheckArgs a = run.args(1, 0);
   a.dbg_block = block;
-  a.dbg_lds = static_cast<v4u*>(lds.p);
-  a.dbg_valu_ops = static_cast<uint32_t*>(ops.p);
-  a.dbg_valu_f32 = static_cast<float*>(f32.p);
-  a.dbg_valu_f64 = static_cast<double*>(f64.p);
-  a.dbg_valu_int = static_cast<unsigned long long*>(i64.p);
-  a.dbg_trans_in = static_cast<float*>(tin.p);
-  a.dbg_trans_out = static_cast<float*>(tout.p);
+  a.dbg_lds = lds.as<v4u>();
+  a.dbg_valu_ops = ops.as<uint32_t>();
+  a.dbg_valu_f32 = f32.as<float>();
+  a.dbg_valu_f64 = f64.as<double>();
+  a.dbg_valu_int = i64.as<unsigned long long>();
+  a.dbg_trans_in = tin.as<float>();
+  a.dbg_trans_out = tout.as<float>();
   run.launch(a);
   AK_HIP(hipDeviceSynchronize());
   run.collect();
+  CuCheckDump d;
   d.hw_id = run.block_loc[2 * block];
   d.xcc_id = run.block_loc[2 * block + 1];
-  AK_HIP(hipMemcpy(d.lds.data(), lds.p, d.lds.size() * 4, hipMemcpyDeviceToHost));
-  AK_HIP(hipMemcpy(d.valu_ops.data(), ops.p, d.valu_ops.size() * 4, hipMemcpyDeviceToHost));
-  AK_HIP(hipMemcpy(d.valu_f32.data(), f32.p, d.valu_f32.size() * 4, hipMemcpyDeviceToHost));
-  AK_HIP(hipMemcpy(d.valu_f64.data(), f64.p, d.valu_f64.size() * 8, hipMemcpyDeviceToHost));
-  AK_HIP(hipMemcpy(d.valu_int.data(), i64.p, d.valu_int.size() * 8, hipMemcpyDeviceToHost));
-  AK_HIP(hipMemcpy(d.trans_in.data(), tin.p, d.trans_in.size() * 4, hipMemcpyDeviceToHost));
-  AK_HIP(hipMemcpy(d.trans_out.data(), tout.p, d.trans_out.size() * 4, hipMemcpyDeviceToHost));
+  d.lds = lds.download<uint32_t>();
+  d.valu_ops = ops.download<uint32_t>();
+  d.valu_f32 = f32.download<float>();
+  d.valu_f64 = f64.download<double>();
+  d.valu_int = i64.download<unsigned long long>();
+  d.trans_in = tin.download<float>();
+  d.trans_out = tout.download<float>();
   return d;
 }
 

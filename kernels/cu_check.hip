@@ -14,9 +14,7 @@
 #include <cstdlib>
 #include <cstring>
 
-#include "gpu_common.h"
-
-static const char* kUnitNames[3] = {"lds", "valu", "trans"};
+#include "cu_check.h"
 
 static void print_location(const amdkube::CuLocation& l) {
   std::printf("\"xcc\":%d,\"se\":%d,\"sh\":%d,\"cu\":%d", l.xcc, l.se, l.sh, l.cu);
@@ -79,7 +77,7 @@ int main(int argc, char** argv) {
     bool first = true;
     for (int u = 0; u < 3; ++u)
       if (units & (1 << u)) {
-        std::printf("%s\"%s\"", first ? "" : ",", kUnitNames[u]);
+        std::printf("%s\"%s\"", first ? "" : ",", amdkube::CU_UNIT_NAMES[u]);
         first = false;
       }
     std::printf("],\"blocks\":%d,\"rounds\":%lld,\"launches\":%d,\"ms\":%.2f,\"lds_gbps\":%.1f,\"valu_gops\":%.1f,"
@@ -95,7 +93,7 @@ int main(int argc, char** argv) {
     std::printf("],\"first_errors\":[");
     for (size_t i = 0; i < r.first_errors.size(); ++i) {
       const amdkube::CuCheckRecord& e = r.first_errors[i];
-      std::printf("%s{\"unit\":\"%s\",\"block\":%u,", i ? "," : "", kUnitNames[e.unit < 3 ? e.unit : 0], e.block);
+      std::printf("%s{\"unit\":\"%s\",\"block\":%u,", i ? "," : "", amdkube::CU_UNIT_NAMES[e.unit < 3 ? e.unit : 0], e.block);
       print_location(amdkube::cu_decode_location(e.hw_id, e.xcc_id));
       std::printf(",\"round\":%u,\"pass\":%u,\"index\":%u,\"got\":%u,\"want\":%u}", e.round, e.pass, e.index, e.got, e.want);
     }

@@ -6,7 +6,7 @@
 #include <cstdlib>
 #include <cstring>
 
-#include "gpu_common.h"
+#include "mfma_check.h"
 
 int main(int argc, char** argv) {
   double ms = 200;

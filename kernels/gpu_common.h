@@ -3,8 +3,9 @@
 // The reference's only GPU workload is the CUDA-samples vectorAdd image its e2e tests run
 // in GPU pods (test/images/cuda-vector-add/Dockerfile:15-26; 50,000 fp32 elements), plus
 // device health that comes solely from the plugin (api.proto:97). amdkube replaces that
-// with five CDNA4-native kernels shared by the standalone pod binaries (rocm-vector-add,
-// hbm-probe, gpu-burn, mfma-check, cu-check) and the in-process Python extension (_hipops):
+// with five CDNA4-native workloads behind the standalone pod binaries (rocm-vector-add,
+// hbm-probe, gpu-burn, mfma-check, cu-check) and the in-process Python extension (_hipops).
+// This header is the base: the first three, and mix32 and the vector types the checks build on.
 //
 //   vector add   wave64 grid-stride, 16-B (float4) loads, grid sized to the chip
 //   HBM probe    address-hashed write / verify / read / copy over buffers larger than
@@ -13,75 +14,25 @@
 //                ~6.3 TB/s; verify counts mismatches (ECC-sensitive health check)
 //   MFMA burn    register-resident v_mfma_f32_32x32x16_bf16 chains, 2 independent
 //                accumulators per wave, for matrix-core load / utilisation validation
+//
+// The checks are headers of their own, each including this one; a program includes what it launches:
 //   MFMA check   (mfma_check.h) LDS-staged 64x64 bf16 tiles whose every result is compared:
 //                round 0 with exact int32 arithmetic, later rounds bitwise with round 0;
 //                (mfma_check_lp.h) the same on the FP8 MFMA and the block-scaled MXFP8 / MXFP4 forms
 //   CU check     (cu_check.h) one workgroup per CU with all 160 KiB of LDS: a march over the LDS, the
 //                same multiply-adds on the fp32, packed-fp32, fp64 and integer pipes, the
 //                transcendental unit on two waves, and the XCD / shader engine / CU it ran on
+// The host side is shared: gpu_host.h (AK_HIP, DevInfo, DevBuf, GpuTimer) and check_core.h (calibration,
+// self-test flip positions, list splitting; plain C++, self-tested on the CPU).
 //
 // Every launch is bounded by construction (grid-stride loops over checked sizes) and uses
 // no inter-workgroup synchronisation, so no launch can hang the device.
 #pragma once
 
-#include <hip/hip_runtime.h>
-
-#include <chrono>
-#include <cstdint>
-#include <cstdio>
-#include <cstring>
-#include <stdexcept>
-#include <string>
-#include <vector>
+#include "check_core.h"
+#include "gpu_host.h"
 
 namespace amdkube {
-
-#define AK_HIP(call)                                                                       \
-  do {                                                                                     \
-    hipError_t e_ = (call);                                                                \
-    if (e_ != hipSuccess)                                                                  \
-      throw std::runtime_error(std::string(#call) + ": " + hipGetErrorString(e_));         \
-  } while (0)
-
-struct DevInfo {
-  std::string name, arch, pci_bus_id, uuid;
-  size_t total_mem = 0;
-  int cu_count = 0;
-  int device = 0;
-};
-
-inline std::string uuid_string(const hipUUID& u) {
-  // HIP reports the 16 raw bytes; AMD exposes them as the ASCII unique id, print both forms
-  bool printable = true;
-  for (int i = 0; i < 16; ++i) {
-    unsigned char c = static_cast<unsigned char>(u.bytes[i]);
-    if (c != 0 && (c < 0x20 || c > 0x7e)) printable = false;
-  }
-  if (printable) {
-    std::string s(u.bytes, u.bytes + 16);
-    s = s.c_str();
-    if (!s.empty()) return "GPU-" + s;
-  }
-  char buf[40];
-  for (int i = 0; i < 16; ++i) std::snprintf(buf + 2 * i, 3, "%02x", static_cast<unsigned char>(u.bytes[i]));
-  return std::string("GPU-") + buf;
-}
-
-inline DevInfo dev_info(int dev) {
-  DevInfo d;
-  d.device = dev;
-  hipDeviceProp_t p;
-  AK_HIP(hipGetDeviceProperties(&p, dev));
-  d.name = p.name;
-  d.arch = p.gcnArchName;
-  d.total_mem = p.totalGlobalMem;
-  d.cu_count = p.multiProcessorCount;
-  char bus[64] = {0};
-  if (hipDeviceGetPCIBusId(bus, sizeof(bus), dev) == hipSuccess) d.pci_bus_id = bus;
-  hipUUID u;
-  if (hipDeviceGetUuid(&u, dev) == hipSuccess) d.uuid = uuid_string(u);
-  return d;
-}
 
 // ---------------------------------------------------------------------------- kernels
 // Each workgroup owns one contiguous chunk of the float4 range (streaming, non-temporal): on
@@ -112,6 +63,11 @@ __device__ __forceinline__ uint32_t mix32(uint32_t x) {
   x *= 0x846ca68bu;
   x ^= x >> 16;
   return x;
+}
+
+// the checks' hash of (seed, workgroup, index)
+__device__ __forceinline__ uint32_t mix32(uint32_t seed, uint32_t block, uint32_t index) {
+  return mix32(mix32(seed ^ (0x9e3779b9u * (block + 1))) + index);
 }
 
 __device__ __forceinline__ uint4 pattern(size_t i, uint32_t seed) {
@@ -294,7 +250,7 @@ inline VaddResult run_vector_add(size_t n, int dev) {
   if (n == 0) throw std::invalid_argument("n must be > 0");
   AK_HIP(hipSetDevice(dev));
   DevInfo info = dev_info(dev);
-  std::vector<float> ha(n), hb(n), hc(n);
+  std::vector<float> ha(n), hb(n);
   uint32_t s = 12345u;
   for (size_t i = 0; i < n; ++i) {
     s = s * 1664525u + 1013904223u;
@@ -302,38 +258,14 @@ inline VaddResult run_vector_add(size_t n, int dev) {
     s = s * 1664525u + 1013904223u;
     hb[i] = static_cast<float>(s >> 8) / 16777216.0f;
   }
-  float *da = nullptr, *db = nullptr, *dc = nullptr;
-  const size_t bytes = n * sizeof(float);
-  AK_HIP(hipMalloc(&da, bytes));
-  AK_HIP(hipMalloc(&db, bytes));
-  AK_HIP(hipMalloc(&dc, bytes));
-  try {
-    AK_HIP(hipMemcpy(da, ha.data(), bytes, hipMemcpyHostToDevice));
-    AK_HIP(hipMemcpy(db, hb.data(), bytes, hipMemcpyHostToDevice));
-    hipEvent_t e0, e1;
-    AK_HIP(hipEventCreate(&e0));
-    AK_HIP(hipEventCreate(&e1));
-    int grid = stream_grid((n + 3) / 4, info.cu_count, VADD_BLOCKS_PER_CU);
-    AK_HIP(hipEventRecord(e0));
-    hipLaunchKernelGGL(vadd_kernel, dim3(grid), dim3(256), 0, 0, da, db, dc, n);
+  DevBuf da(ha), db(hb), dc(n * sizeof(float));
+  GpuTimer timer;
+  const int grid = stream_grid((n + 3) / 4, info.cu_count, VADD_BLOCKS_PER_CU);
+  r.kernel_ms = timer.time([&] {
+    hipLaunchKernelGGL(vadd_kernel, dim3(grid), dim3(256), 0, 0, da.as<float>(), db.as<float>(), dc.as<float>(), n);
     AK_HIP(hipGetLastError());
-    AK_HIP(hipEventRecord(e1));
-    AK_HIP(hipEventSynchronize(e1));
-    float ms = 0;
-    AK_HIP(hipEventElapsedTime(&ms, e0, e1));
-    r.kernel_ms = ms;
-    AK_HIP(hipMemcpy(hc.data(), dc, bytes, hipMemcpyDeviceToHost));
-    hipEventDestroy(e0);
-    hipEventDestroy(e1);
-  } catch (...) {
-    hipFree(da);
-    hipFree(db);
-    hipFree(dc);
-    throw;
-  }
-  hipFree(da);
-  hipFree(db);
-  hipFree(dc);
+  });
+  const std::vector<float> hc = dc.download<float>();
   for (size_t i = 0; i < n; ++i) {
     float d = hc[i] - (ha[i] + hb[i]);
     if (d > 1e-5f || d < -1e-5f) ++r.mismatches;
@@ -343,29 +275,16 @@ inline VaddResult run_vector_add(size_t n, int dev) {
 }
 
 // ---- host-supplied data: the kernels on caller-provided inputs (numerics vs torch fp32)
-struct DevBuf {
-  void* p = nullptr;
-  explicit DevBuf(size_t n) { AK_HIP(hipMalloc(&p, n ? n : 16)); }
-  ~DevBuf() { hipFree(p); }
-  DevBuf(const DevBuf&) = delete;
-  DevBuf& operator=(const DevBuf&) = delete;
-};
-
 // c = a + b on the device with the pod workload's vadd_kernel
 inline std::vector<float> vector_add_host(const std::vector<float>& a, const std::vector<float>& b, int dev) {
   if (a.size() != b.size()) throw std::invalid_argument("a and b differ in length");
   AK_HIP(hipSetDevice(dev));
-  const size_t n = a.size(), bytes = n * sizeof(float);
-  DevBuf da(bytes), db(bytes), dc(bytes);
-  AK_HIP(hipMemcpy(da.p, a.data(), bytes, hipMemcpyHostToDevice));
-  AK_HIP(hipMemcpy(db.p, b.data(), bytes, hipMemcpyHostToDevice));
+  const size_t n = a.size();
+  DevBuf da(a), db(b), dc(n * sizeof(float));
   const int grid = stream_grid((n + 3) / 4, dev_info(dev).cu_count, VADD_BLOCKS_PER_CU);
-  hipLaunchKernelGGL(vadd_kernel, dim3(grid), dim3(256), 0, 0, static_cast<const float*>(da.p),
-                     static_cast<const float*>(db.p), static_cast<float*>(dc.p), n);
+  hipLaunchKernelGGL(vadd_kernel, dim3(grid), dim3(256), 0, 0, da.as<const float>(), db.as<const float>(), dc.as<float>(), n);
   AK_HIP(hipGetLastError());
-  std::vector<float> c(n);
-  AK_HIP(hipMemcpy(c.data(), dc.p, bytes, hipMemcpyDeviceToHost));
-  return c;
+  return dc.download<float>();
 }
 
 // the HBM probe's write pattern for n16 16-byte words (checked against a torch re-derivation)
@@ -373,11 +292,9 @@ inline std::vector<uint32_t> hbm_pattern_host(size_t n16, uint32_t seed, int dev
   AK_HIP(hipSetDevice(dev));
   DevBuf d(n16 * 16);
   const int grid = write_front_grid(dev_info(dev).cu_count);
-  hipLaunchKernelGGL(hbm_write_kernel, dim3(grid), dim3(256), 0, 0, static_cast<v4u*>(d.p), n16, seed);
+  hipLaunchKernelGGL(hbm_write_kernel, dim3(grid), dim3(256), 0, 0, d.as<v4u>(), n16, seed);
   AK_HIP(hipGetLastError());
-  std::vector<uint32_t> out(n16 * 4);
-  AK_HIP(hipMemcpy(out.data(), d.p, n16 * 16, hipMemcpyDeviceToHost));
-  return out;
+  return d.download<uint32_t>();
 }
 
 // the probe's verify kernel on caller data: mismatching 32-bit words against the pattern
@@ -385,16 +302,11 @@ inline unsigned long long hbm_verify_host(const std::vector<uint32_t>& words, ui
   if (words.size() % 4) throw std::invalid_argument("need a whole number of 16-byte words");
   AK_HIP(hipSetDevice(dev));
   const size_t n16 = words.size() / 4;
-  DevBuf d(n16 * 16), e(sizeof(unsigned long long));
-  AK_HIP(hipMemcpy(d.p, words.data(), n16 * 16, hipMemcpyHostToDevice));
-  AK_HIP(hipMemset(e.p, 0, sizeof(unsigned long long)));
+  DevBuf d(words), e(sizeof(unsigned long long), DevBuf::zeroed);
   const int grid = stream_grid(n16, dev_info(dev).cu_count, HBM_BLOCKS_PER_CU);
-  hipLaunchKernelGGL(hbm_verify_kernel, dim3(grid), dim3(256), 0, 0, static_cast<const v4u*>(d.p), n16, seed,
-                     static_cast<unsigned long long*>(e.p));
+  hipLaunchKernelGGL(hbm_verify_kernel, dim3(grid), dim3(256), 0, 0, d.as<const v4u>(), n16, seed, e.as<unsigned long long>());
   AK_HIP(hipGetLastError());
-  unsigned long long bad = 0;
-  AK_HIP(hipMemcpy(&bad, e.p, sizeof(bad), hipMemcpyDeviceToHost));
-  return bad;
+  return e.download<unsigned long long>()[0];
 }
 
 // the probe's copy kernel on caller data
@@ -402,15 +314,11 @@ inline std::vector<uint32_t> hbm_copy_host(const std::vector<uint32_t>& words, i
   if (words.size() % 4) throw std::invalid_argument("need a whole number of 16-byte words");
   AK_HIP(hipSetDevice(dev));
   const size_t n16 = words.size() / 4;
-  DevBuf s(n16 * 16), d(n16 * 16);
-  AK_HIP(hipMemcpy(s.p, words.data(), n16 * 16, hipMemcpyHostToDevice));
+  DevBuf s(words), d(n16 * 16);
   const int grid = stream_grid(n16, dev_info(dev).cu_count, HBM_COPY_BLOCKS_PER_CU);
-  hipLaunchKernelGGL(hbm_copy_kernel, dim3(grid), dim3(256), 0, 0, static_cast<const v4u*>(s.p), static_cast<v4u*>(d.p),
-                     n16);
+  hipLaunchKernelGGL(hbm_copy_kernel, dim3(grid), dim3(256), 0, 0, s.as<const v4u>(), d.as<v4u>(), n16);
   AK_HIP(hipGetLastError());
-  std::vector<uint32_t> out(words.size());
-  AK_HIP(hipMemcpy(out.data(), d.p, n16 * 16, hipMemcpyDeviceToHost));
-  return out;
+  return d.download<uint32_t>();
 }
 
 // C[32x32] fp32 = A[32xK] bf16 * B[Kx32] bf16 on one wave (K a multiple of 16, <= 1024)
@@ -420,15 +328,11 @@ inline std::vector<float> mfma_tile_host(const std::vector<uint16_t>& a_bits, co
   if (a_bits.size() != static_cast<size_t>(32 * k) || b_bits.size() != static_cast<size_t>(32 * k))
     throw std::invalid_argument("A must be 32xK and B Kx32 bf16");
   AK_HIP(hipSetDevice(dev));
-  DevBuf da(a_bits.size() * 2), db(b_bits.size() * 2), dc(32 * 32 * sizeof(float));
-  AK_HIP(hipMemcpy(da.p, a_bits.data(), a_bits.size() * 2, hipMemcpyHostToDevice));
-  AK_HIP(hipMemcpy(db.p, b_bits.data(), b_bits.size() * 2, hipMemcpyHostToDevice));
-  hipLaunchKernelGGL(mfma_tile_kernel, dim3(1), dim3(64), 0, 0, static_cast<const __bf16*>(da.p),
-                     static_cast<const __bf16*>(db.p), static_cast<float*>(dc.p), k / 16);
+  DevBuf da(a_bits), db(b_bits), dc(32 * 32 * sizeof(float));
+  hipLaunchKernelGGL(mfma_tile_kernel, dim3(1), dim3(64), 0, 0, da.as<const __bf16>(), db.as<const __bf16>(), dc.as<float>(),
+                     k / 16);
   AK_HIP(hipGetLastError());
-  std::vector<float> c(32 * 32);
-  AK_HIP(hipMemcpy(c.data(), dc.p, c.size() * sizeof(float), hipMemcpyDeviceToHost));
-  return c;
+  return dc.download<float>();
 }
 
 struct HbmResult {
@@ -446,52 +350,30 @@ inline HbmResult run_hbm_probe(size_t bytes, int iters, int dev, uint32_t seed =
   AK_HIP(hipSetDevice(dev));
   DevInfo info = dev_info(dev);
   const size_t n16 = bytes / 16;
-  v4u *a = nullptr, *b = nullptr;
-  unsigned long long* errs = nullptr;
-  uint32_t* sink = nullptr;
-  AK_HIP(hipMalloc(&a, bytes));
-  if (hipMalloc(&b, bytes) != hipSuccess) {
-    hipFree(a);
-    throw std::runtime_error("hipMalloc failed for hbm probe buffer");
-  }
-  AK_HIP(hipMalloc(&errs, sizeof(unsigned long long)));
-  AK_HIP(hipMalloc(&sink, sizeof(uint32_t)));
-  AK_HIP(hipMemset(errs, 0, sizeof(unsigned long long)));
-  hipEvent_t e0, e1;
-  AK_HIP(hipEventCreate(&e0));
-  AK_HIP(hipEventCreate(&e1));
+  DevBuf da(bytes), db(bytes), derrs(sizeof(unsigned long long), DevBuf::zeroed), dsink(sizeof(uint32_t));
+  v4u *a = da.as<v4u>(), *b = db.as<v4u>();
+  unsigned long long* errs = derrs.as<unsigned long long>();
+  uint32_t* sink = dsink.as<uint32_t>();
+  GpuTimer timer;
   const int grid = stream_grid(n16, info.cu_count, HBM_BLOCKS_PER_CU);
   auto timed = [&](auto&& launch) {
     for (int w = 0; w < 3; ++w) launch();  // warm-up: page-in / first touch, and the clock ramp
     AK_HIP(hipGetLastError());
-    AK_HIP(hipEventRecord(e0));
-    for (int it = 0; it < iters; ++it) launch();
-    AK_HIP(hipEventRecord(e1));
-    AK_HIP(hipEventSynchronize(e1));
-    float ms = 0;
-    AK_HIP(hipEventElapsedTime(&ms, e0, e1));
-    return static_cast<double>(ms) / iters;
+    return timer.time([&] {
+      for (int it = 0; it < iters; ++it) launch();
+    }) / iters;
   };
   const int write_grid = write_front_grid(info.cu_count);
   double w = timed([&] { hipLaunchKernelGGL(hbm_write_kernel, dim3(write_grid), dim3(256), 0, 0, a, n16, seed); });
   double rd = timed([&] { hipLaunchKernelGGL(hbm_read_kernel, dim3(grid), dim3(256), 0, 0, a, n16, sink); });
   const int copy_grid = stream_grid(n16, info.cu_count, HBM_COPY_BLOCKS_PER_CU);
   double cp = timed([&] { hipLaunchKernelGGL(hbm_copy_kernel, dim3(copy_grid), dim3(256), 0, 0, a, b, n16); });
-  AK_HIP(hipMemset(errs, 0, sizeof(unsigned long long)));
-  AK_HIP(hipEventRecord(e0));
-  hipLaunchKernelGGL(hbm_verify_kernel, dim3(grid), dim3(256), 0, 0, b, n16, seed, errs);
-  AK_HIP(hipGetLastError());
-  AK_HIP(hipEventRecord(e1));
-  AK_HIP(hipEventSynchronize(e1));
-  float vms = 0;
-  AK_HIP(hipEventElapsedTime(&vms, e0, e1));
-  AK_HIP(hipMemcpy(&r.errors, errs, sizeof(r.errors), hipMemcpyDeviceToHost));
-  hipEventDestroy(e0);
-  hipEventDestroy(e1);
-  hipFree(a);
-  hipFree(b);
-  hipFree(errs);
-  hipFree(sink);
+  derrs.zero();
+  const double vms = timer.time([&] {
+    hipLaunchKernelGGL(hbm_verify_kernel, dim3(grid), dim3(256), 0, 0, b, n16, seed, errs);
+    AK_HIP(hipGetLastError());
+  });
+  r.errors = derrs.download<unsigned long long>()[0];
   r.bytes = bytes;
   r.iters = iters;
   r.write_gbps = bytes / (w * 1e6);
@@ -512,47 +394,22 @@ inline BurnResult run_mfma_burn(double target_ms, int dev) {
   AK_HIP(hipSetDevice(dev));
   DevInfo info = dev_info(dev);
   const int blocks = (info.cu_count > 0 ? info.cu_count : 256) * 4;  // 16 waves / CU
-  float* out = nullptr;
-  AK_HIP(hipMalloc(&out, static_cast<size_t>(blocks) * 256 * sizeof(float)));
-  hipEvent_t e0, e1;
-  AK_HIP(hipEventCreate(&e0));
-  AK_HIP(hipEventCreate(&e1));
-  auto run = [&](int iters) {
-    AK_HIP(hipEventRecord(e0));
-    hipLaunchKernelGGL(mfma_burn_kernel, dim3(blocks), dim3(256), 0, 0, out, iters);
-    AK_HIP(hipGetLastError());
-    AK_HIP(hipEventRecord(e1));
-    AK_HIP(hipEventSynchronize(e1));
-    float ms = 0;
-    AK_HIP(hipEventElapsedTime(&ms, e0, e1));
-    return static_cast<double>(ms);
-  };
-  int iters = 2000;
-  double ms = run(iters);  // warm-up: code-object load and clock ramp inflate the first launch
-  // calibrate on a launch long enough (>= 20 ms) that launch overhead does not skew the rate
-  while (ms < 20.0 && iters < 200000000) {
-    iters *= 4;
-    ms = run(iters);
-  }
-  if (target_ms > ms && ms > 0) {
-    double scale = target_ms / ms;
-    double want = iters * scale;
-    iters = want > 2.0e9 ? 2000000000 : static_cast<int>(want);
-    ms = run(iters);
-  }
-  hipEventDestroy(e0);
-  hipEventDestroy(e1);
-  hipFree(out);
-  const double flops = static_cast<double>(blocks) * 4 /*waves*/ * iters * 2 /*chains*/ * (2.0 * 32 * 32 * 16);
-  r.ms = ms;
-  r.iters = iters;
+  DevBuf out(static_cast<size_t>(blocks) * 256 * sizeof(float));
+  GpuTimer timer;
+  const Calibrated c = calibrate(
+      [&](int iters, int) {
+        return timer.time([&] {
+          hipLaunchKernelGGL(mfma_burn_kernel, dim3(blocks), dim3(256), 0, 0, out.as<float>(), iters);
+          AK_HIP(hipGetLastError());
+        });
+      },
+      2000, 200000000, 0, target_ms, 0);
+  const double flops = static_cast<double>(blocks) * 4 /*waves*/ * c.rounds * 2 /*chains*/ * (2.0 * 32 * 32 * 16);
+  r.ms = c.ms;
+  r.iters = c.rounds;
   r.blocks = blocks;
-  r.tflops = flops / (ms * 1e9);
+  r.tflops = flops / (c.ms * 1e9);
   return r;
 }
 
 }  // namespace amdkube
-
-#include "mfma_check.h"  // the checked matrix-core workload: mfma_gemm_kernel, mfma_check_kernel, their runners
-#include "mfma_check_lp.h"  // the same for the FP8, MXFP8 and MXFP4 matrix-core paths
-#include "cu_check.h"  // the per-CU check: LDS march, vector ALU and transcendental cross-checks, workgroup placement

@@ -1,7 +1,8 @@
 // Checked matrix-core workload: a 64x64 bf16 MFMA tile staged through LDS, a GEMM on caller data
 // (the numerics surface of the tests) and the integrity check behind mfma-check, gpu-burn --verify
-// and the device plugin's mfma health probe. Included by gpu_common.h, which provides mix32,
-// bf16x8 / f32x16, AK_HIP and DevBuf.
+// and the device plugin's mfma health probe. gpu_common.h provides mix32, bf16x8 / f32x16 and the
+// host plumbing. The run type and its driver serve every format: mfma_check_lp.h adds the FP8 and MX
+// kernels and the dispatch over formats; this header alone is the bf16 check (gpu-burn --verify).
 //
 // The check is the gpu-burn scheme anchored to an exact reference: every workgroup multiplies its
 // own hashed integer operands, compares round 0 against int32 VALU arithmetic bit for bit, then
@@ -10,6 +11,8 @@
 // non-zero error count. All loops are bounded, there is no inter-workgroup synchronisation and
 // every __syncthreads sits in uniform control flow.
 #pragma once
+
+#include "gpu_common.h"
 
 namespace amdkube {
 
@@ -94,10 +97,6 @@ __global__ __launch_bounds__(256) void mfma_gemm_kernel(const __bf16* __restrict
 struct MfmaCheckRecord {
   uint32_t block, row, col, round, got, want;
 };
-
-__device__ __forceinline__ uint32_t mix32(uint32_t seed, uint32_t block, uint32_t index) {
-  return mix32(mix32(seed ^ (0x9e3779b9u * (block + 1))) + index);
-}
 
 // operand value: an integer in [-8, 8], exact in bf16
 __device__ __forceinline__ float mfma_check_value(uint32_t seed, uint32_t block, uint32_t index) {
@@ -221,16 +220,11 @@ inline std::vector<float> mfma_gemm_host(const std::vector<uint16_t>& a_bits, co
   if (a_bits.size() != static_cast<size_t>(m) * k || b_bits.size() != static_cast<size_t>(k) * n)
     throw std::invalid_argument("A must be MxK and B KxN bf16");
   AK_HIP(hipSetDevice(dev));
-  const size_t cn = static_cast<size_t>(m) * n;
-  DevBuf da(a_bits.size() * 2), db(b_bits.size() * 2), dc(cn * sizeof(float));
-  AK_HIP(hipMemcpy(da.p, a_bits.data(), a_bits.size() * 2, hipMemcpyHostToDevice));
-  AK_HIP(hipMemcpy(db.p, b_bits.data(), b_bits.size() * 2, hipMemcpyHostToDevice));
-  hipLaunchKernelGGL(mfma_gemm_kernel, dim3(static_cast<unsigned>(tiles)), dim3(256), 0, 0, static_cast<const __bf16*>(da.p),
-                     static_cast<const __bf16*>(db.p), static_cast<float*>(dc.p), m, n, k);
+  DevBuf da(a_bits), db(b_bits), dc(static_cast<size_t>(m) * n * sizeof(float));
+  hipLaunchKernelGGL(mfma_gemm_kernel, dim3(static_cast<unsigned>(tiles)), dim3(256), 0, 0, da.as<const __bf16>(),
+                     db.as<const __bf16>(), dc.as<float>(), m, n, k);
   AK_HIP(hipGetLastError());
-  std::vector<float> c(cn);
-  AK_HIP(hipMemcpy(c.data(), dc.p, cn * sizeof(float), hipMemcpyDeviceToHost));
-  return c;
+  return dc.download<float>();
 }
 
 inline int mfma_check_blocks(int cu_count) { return (cu_count > 0 ? cu_count : 256) * MFMA_CHECK_BLOCKS_PER_CU; }
@@ -243,107 +237,65 @@ struct MfmaCheckResult {
   std::vector<MfmaCheckRecord> first_errors;
 };
 
-// Device buffers and the launch of one check; errors and records accumulate over launches.
+// Device buffers of one check and the launch of its format; errors and records accumulate over launches.
 struct MfmaCheckRun {
+  // queues one launch of a format's check kernel on the run's buffers
+  using Kernel = void (*)(const MfmaCheckRun& run, int rounds, int flips, int dbg_block, float* dbg_a, float* dbg_b,
+                          float* dbg_c);
   int blocks, k;
   uint32_t seed;
+  Kernel kernel;
   DevBuf errors, nrec, recs, flip_pos;
-  MfmaCheckRun(int dev, uint32_t seed_, int k_total)
-      : blocks(mfma_check_blocks(dev_info(dev).cu_count)), k(k_total), seed(seed_), errors(sizeof(unsigned long long)),
-        nrec(sizeof(unsigned)), recs(MFMA_CHECK_RECORDS * sizeof(MfmaCheckRecord)),
-        flip_pos(MFMA_CHECK_MAX_FLIPS * sizeof(uint32_t)) {
-    if (k < 16 || k > MFMA_CHECK_KMAX || k % 16) throw std::invalid_argument("k must be a multiple of 16 in [16, 128]");
-    AK_HIP(hipMemset(errors.p, 0, sizeof(unsigned long long)));
-    AK_HIP(hipMemset(nrec.p, 0, sizeof(unsigned)));
-    AK_HIP(hipMemset(recs.p, 0, MFMA_CHECK_RECORDS * sizeof(MfmaCheckRecord)));
-    // flip positions: (base + i * stride) mod (blocks * 4096) with the stride coprime to the modulus,
-    // so the positions are distinct
-    const unsigned long long positions = static_cast<unsigned long long>(blocks) * (MFMA_TILE * MFMA_TILE);
-    auto gcd = [](unsigned long long a, unsigned long long b) {
-      while (b) {
-        const unsigned long long r = a % b;
-        a = b;
-        b = r;
-      }
-      return a;
-    };
-    const unsigned long long base = (seed * 2654435761ull + 0x5bd1e995u) % positions;
-    unsigned long long stride = (((seed ^ 0x9e3779b9u) * 0x85ebca6bull) % positions) | 1;
-    while (gcd(stride, positions) != 1) stride += 2;
-    std::vector<uint32_t> pos(MFMA_CHECK_MAX_FLIPS);
-    for (size_t i = 0; i < pos.size(); ++i) pos[i] = static_cast<uint32_t>((base + i * stride) % positions);
-    AK_HIP(hipMemcpy(flip_pos.p, pos.data(), pos.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
-  }
+  // flip positions: distinct tile positions block * 4096 + row * 64 + col
+  MfmaCheckRun(int dev, uint32_t seed_, int k_total, Kernel kernel_)
+      : blocks(mfma_check_blocks(dev_info(dev).cu_count)), k(k_total), seed(seed_), kernel(kernel_),
+        errors(sizeof(unsigned long long), DevBuf::zeroed), nrec(sizeof(unsigned), DevBuf::zeroed),
+        recs(MFMA_CHECK_RECORDS * sizeof(MfmaCheckRecord), DevBuf::zeroed),
+        flip_pos(flip_positions(seed_, MFMA_CHECK_MAX_FLIPS, static_cast<unsigned long long>(blocks) * (MFMA_TILE * MFMA_TILE))) {}
   void launch(int rounds, int flips, int dbg_block = -1, float* dbg_a = nullptr, float* dbg_b = nullptr,
-              float* dbg_c = nullptr) {
-    hipLaunchKernelGGL(mfma_check_kernel, dim3(blocks), dim3(256), 0, 0, seed, k, rounds, flips,
-                       static_cast<const uint32_t*>(flip_pos.p), static_cast<unsigned long long*>(errors.p),
-                       static_cast<unsigned*>(nrec.p),
-                       static_cast<MfmaCheckRecord*>(recs.p), dbg_block, dbg_a, dbg_b, dbg_c);
+              float* dbg_c = nullptr) const {
+    kernel(*this, rounds, flips, dbg_block, dbg_a, dbg_b, dbg_c);
     AK_HIP(hipGetLastError());
   }
 };
 
-// rounds > 0: one launch of exactly that many rounds. rounds <= 0: calibrate to ~target_ms as
-// run_mfma_burn does (the self-test flips then go into the last launch only).
-// Shared by the low-precision checks (mfma_check_lp.h): Run provides launch(rounds, flips), blocks, k
-// and the errors / nrec / recs buffers.
-template <class Run>
-inline MfmaCheckResult mfma_check_drive(Run& run, int rounds, double target_ms, int flips) {
-  hipEvent_t e0, e1;
-  AK_HIP(hipEventCreate(&e0));
-  AK_HIP(hipEventCreate(&e1));
-  auto timed = [&](int r, int f) {
-    AK_HIP(hipEventRecord(e0));
-    run.launch(r, f);
-    AK_HIP(hipEventRecord(e1));
-    AK_HIP(hipEventSynchronize(e1));
-    float ms = 0;
-    AK_HIP(hipEventElapsedTime(&ms, e0, e1));
-    return static_cast<double>(ms);
-  };
-  double ms;
-  if (rounds > 0) {
-    ms = timed(rounds, flips);
-  } else {
-    rounds = 256;
-    ms = timed(rounds, 0);  // warm-up: code-object load and clock ramp inflate the first launch
-    while (ms < 20.0 && rounds < (1 << 26)) {
-      rounds *= 4;
-      ms = timed(rounds, 0);
-    }
-    const bool longer = target_ms > ms && ms > 0;
-    if (longer) {
-      const double want = rounds * (target_ms / ms);
-      rounds = want > 2.0e9 ? 2000000000 : static_cast<int>(want);
-    }
-    if (longer || flips > 0) ms = timed(rounds, flips);
-  }
-  hipEventDestroy(e0);
-  hipEventDestroy(e1);
+inline void mfma_check_launch_bf16(const MfmaCheckRun& run, int rounds, int flips, int dbg_block, float* dbg_a, float* dbg_b,
+                                   float* dbg_c) {
+  hipLaunchKernelGGL(mfma_check_kernel, dim3(run.blocks), dim3(256), 0, 0, run.seed, run.k, rounds, flips,
+                     run.flip_pos.as<const uint32_t>(), run.errors.as<unsigned long long>(), run.nrec.as<unsigned>(),
+                     run.recs.as<MfmaCheckRecord>(), dbg_block, dbg_a, dbg_b, dbg_c);
+}
+
+// One check of `kernel`'s format at K = k. rounds > 0: one launch of exactly that many rounds.
+// rounds <= 0: calibrated to ~target_ms (check_core.h; the self-test flips go into the last launch only).
+inline MfmaCheckResult mfma_check_drive(MfmaCheckRun::Kernel kernel, int k, int rounds, double target_ms, int dev,
+                                        uint32_t seed, int flips) {
+  if (flips < 0 || flips > MFMA_CHECK_MAX_FLIPS) throw std::invalid_argument("selftest flips must be in [0, 4096]");
+  AK_HIP(hipSetDevice(dev));
+  MfmaCheckRun run(dev, seed, k, kernel);
+  GpuTimer timer;
+  const Calibrated c =
+      calibrate([&](int r, int f) { return timer.time([&] { run.launch(r, f); }); }, 256, 1 << 26, rounds, target_ms, flips);
   MfmaCheckResult r;
-  unsigned n = 0;
-  AK_HIP(hipMemcpy(&r.errors, run.errors.p, sizeof(r.errors), hipMemcpyDeviceToHost));
-  AK_HIP(hipMemcpy(&n, run.nrec.p, sizeof(n), hipMemcpyDeviceToHost));
-  r.first_errors.resize(n < static_cast<unsigned>(MFMA_CHECK_RECORDS) ? n : MFMA_CHECK_RECORDS);
-  if (!r.first_errors.empty())
-    AK_HIP(hipMemcpy(r.first_errors.data(), run.recs.p, r.first_errors.size() * sizeof(MfmaCheckRecord),
-                     hipMemcpyDeviceToHost));
-  r.ms = ms;
-  r.rounds = rounds;
+  r.errors = run.errors.download<unsigned long long>()[0];
+  r.first_errors = fetch_records<MfmaCheckRecord>(run.nrec, run.recs);
+  r.ms = c.ms;
+  r.rounds = c.rounds;
   r.blocks = run.blocks;
-  r.k = run.k;
+  r.k = k;
   // every round is a full MFMA product of the tile, round 0 included
-  r.tflops = static_cast<double>(run.blocks) * rounds * (2.0 * MFMA_TILE * MFMA_TILE * run.k) / (ms * 1e9);
+  r.tflops = static_cast<double>(run.blocks) * c.rounds * (2.0 * MFMA_TILE * MFMA_TILE * k) / (c.ms * 1e9);
   return r;
+}
+
+inline int mfma_check_bf16_k(int k) {
+  if (k < 16 || k > MFMA_CHECK_KMAX || k % 16) throw std::invalid_argument("k must be a multiple of 16 in [16, 128]");
+  return k;
 }
 
 inline MfmaCheckResult run_mfma_check(int rounds, double target_ms, int dev, uint32_t seed = 0x5eedu, int flips = 0,
                                       int k_total = MFMA_CHECK_KMAX) {
-  if (flips < 0 || flips > MFMA_CHECK_MAX_FLIPS) throw std::invalid_argument("selftest flips must be in [0, 4096]");
-  AK_HIP(hipSetDevice(dev));
-  MfmaCheckRun run(dev, seed, k_total);
-  return mfma_check_drive(run, rounds, target_ms, flips);
+  return mfma_check_drive(mfma_check_launch_bf16, mfma_check_bf16_k(k_total), rounds, target_ms, dev, seed, flips);
 }
 
 struct MfmaCheckTile {
@@ -352,27 +304,19 @@ struct MfmaCheckTile {
 };
 
 // one launch of a single round with workgroup `block` storing its operands and product
-template <class Run>
-inline MfmaCheckTile mfma_check_fetch_tile(Run& run, int block) {
+inline MfmaCheckTile mfma_check_fetch_tile(MfmaCheckRun::Kernel kernel, int k, int block, uint32_t seed, int dev) {
+  AK_HIP(hipSetDevice(dev));
+  MfmaCheckRun run(dev, seed, k, kernel);
   if (block < 0 || block >= run.blocks) throw std::invalid_argument("block out of range");
-  MfmaCheckTile t;
-  t.k = run.k;
-  const size_t nab = static_cast<size_t>(MFMA_TILE) * run.k, nc = static_cast<size_t>(MFMA_TILE) * MFMA_TILE;
+  const size_t nab = static_cast<size_t>(MFMA_TILE) * k, nc = static_cast<size_t>(MFMA_TILE) * MFMA_TILE;
   DevBuf da(nab * sizeof(float)), db(nab * sizeof(float)), dc(nc * sizeof(float));
-  run.launch(1, 0, block, static_cast<float*>(da.p), static_cast<float*>(db.p), static_cast<float*>(dc.p));
-  t.a.resize(nab);
-  t.b.resize(nab);
-  t.c.resize(nc);
-  AK_HIP(hipMemcpy(t.a.data(), da.p, nab * sizeof(float), hipMemcpyDeviceToHost));
-  AK_HIP(hipMemcpy(t.b.data(), db.p, nab * sizeof(float), hipMemcpyDeviceToHost));
-  AK_HIP(hipMemcpy(t.c.data(), dc.p, nc * sizeof(float), hipMemcpyDeviceToHost));
-  return t;
+  run.launch(1, 0, block, da.as<float>(), db.as<float>(), dc.as<float>());
+  return MfmaCheckTile{k, da.download<float>(), db.download<float>(), dc.download<float>()};
 }
 
 inline MfmaCheckTile mfma_check_tile_host(int block, uint32_t seed, int dev, int k_total = MFMA_CHECK_KMAX) {
-  AK_HIP(hipSetDevice(dev));
-  MfmaCheckRun run(dev, seed, k_total);
-  return mfma_check_fetch_tile(run, block);
+  return mfma_check_fetch_tile(mfma_check_launch_bf16, mfma_check_bf16_k(k_total), block, seed, dev);
 }
 
 }  // namespace amdkube
+

@@ -9,11 +9,10 @@
 // e4m3 / e2m1 forms, kernels/mfma_check_lp.h): one JSON line per dtype in the order given, each
 // with "dtype" and "tflops", stopping after the first dtype with mismatches; the other flags apply
 // to each dtype. Exit 2 on an unknown dtype, 4 on a runtime error.
-#include <algorithm>
 #include <cstdlib>
 #include <cstring>
 
-#include "gpu_common.h"
+#include "mfma_check_lp.h"
 
 static void print_errors(const amdkube::MfmaCheckResult& r) {
   std::printf("\"errors\":%llu,\"first_errors\":[", r.errors);
@@ -38,41 +37,26 @@ int main(int argc, char** argv) {
     else if (!std::strcmp(argv[i], "--selftest-flips") && i + 1 < argc) flips = std::atoi(argv[++i]);
     else if (!std::strcmp(argv[i], "--dtype") && i + 1 < argc) dtypes = argv[++i];
   }
-  // -1 is bf16, otherwise an MfmaLpFmt; every name is checked before anything runs
+  // without --dtype: the bf16 check, printed without "dtype" and "tflops". Every name is checked before anything runs
   std::vector<int> fmts;
-  if (dtypes) {
-    const std::string list = dtypes;
-    for (size_t at = 0; at <= list.size();) {
-      const size_t end = std::min(list.find(',', at), list.size());
-      const std::string name = list.substr(at, end - at);
-      try {
-        fmts.push_back(name == "bf16" ? -1 : amdkube::mfma_lp_fmt(name));
-      } catch (const std::invalid_argument&) {
-        std::fprintf(stderr, "mfma-check: unknown dtype '%s': expected a comma list over bf16, fp8, mxfp8, mxfp4\n",
-                     name.c_str());
-        return 2;
-      }
-      at = end + 1;
+  for (const std::string& name : amdkube::split_list(dtypes ? dtypes : "bf16")) {
+    try {
+      fmts.push_back(amdkube::mfma_lp_fmt(name, amdkube::MFMA_BF16));
+    } catch (const std::invalid_argument&) {
+      std::fprintf(stderr, "mfma-check: unknown dtype '%s': expected a comma list over bf16, fp8, mxfp8, mxfp4\n",
+                   name.c_str());
+      return 2;
     }
   }
   try {
     amdkube::DevInfo d = amdkube::dev_info(dev);
-    if (!dtypes) {
-      amdkube::MfmaCheckResult r = amdkube::run_mfma_check(rounds, ms, dev, seed, flips);
-      std::printf("{\"device\":%d,\"uuid\":\"%s\",\"arch\":\"%s\",\"blocks\":%d,\"rounds\":%lld,\"k\":%d,\"ms\":%.2f,"
-                  "\"bf16_tflops\":%.1f,",
-                  dev, d.uuid.c_str(), d.arch.c_str(), r.blocks, r.rounds, r.k, r.ms, r.tflops);
-      print_errors(r);
-      return r.errors ? 1 : 0;
-    }
     for (int f : fmts) {
-      amdkube::MfmaCheckResult r = f < 0 ? amdkube::run_mfma_check(rounds, ms, dev, seed, flips)
-                                         : amdkube::run_mfma_check_lp(f, rounds, ms, dev, seed, flips);
-      std::printf("{\"device\":%d,\"uuid\":\"%s\",\"arch\":\"%s\",\"dtype\":\"%s\",\"blocks\":%d,\"rounds\":%lld,\"k\":%d,"
-                  "\"ms\":%.2f,",
-                  dev, d.uuid.c_str(), d.arch.c_str(), f < 0 ? "bf16" : amdkube::mfma_lp_name(f), r.blocks, r.rounds, r.k, r.ms);
-      if (f < 0) std::printf("\"bf16_tflops\":%.1f,", r.tflops);
-      std::printf("\"tflops\":%.1f,", r.tflops);
+      amdkube::MfmaCheckResult r = amdkube::run_mfma_check_lp(f, rounds, ms, dev, seed, flips);
+      std::printf("{\"device\":%d,\"uuid\":\"%s\",\"arch\":\"%s\",", dev, d.uuid.c_str(), d.arch.c_str());
+      if (dtypes) std::printf("\"dtype\":\"%s\",", amdkube::mfma_lp_name(f));
+      std::printf("\"blocks\":%d,\"rounds\":%lld,\"k\":%d,\"ms\":%.2f,", r.blocks, r.rounds, r.k, r.ms);
+      if (f == amdkube::MFMA_BF16) std::printf("\"bf16_tflops\":%.1f,", r.tflops);
+      if (dtypes) std::printf("\"tflops\":%.1f,", r.tflops);
       print_errors(r);
       std::fflush(stdout);
       if (r.errors) return 1;  // the failing line is the last one printed

@@ -1,6 +1,6 @@
 // Low-precision matrix-core check: the 64x64 tile, GEMM and integrity check of mfma_check.h for the
-// FP8 and block-scaled MX paths of CDNA4. Included by gpu_common.h after mfma_check.h, whose record
-// buffer, error counter, flip mask, compare and flip-position scheme it reuses unchanged.
+// FP8 and block-scaled MX paths of CDNA4, on the run type, driver, record buffer, flip mask and
+// compare of mfma_check.h. mfma_fmt_ops is the one table from a format, bf16 included, to its kernels.
 //
 //   fp8    v_mfma_f32_32x32x16_fp8_fp8, OCP e4m3fn operands, K step 16
 //   mxfp8  v_mfma_scale_f32_32x32x64_f8f6f4, cbsz = blgp = 0 (e4m3), one E8M0 scale per 32 k, K step 64
@@ -21,9 +21,12 @@
 // The C/D map is the bf16 one (mfma_tile64_row / mfma_tile64_col).
 #pragma once
 
+#include "mfma_check.h"
+
 namespace amdkube {
 
-enum MfmaLpFmt { MFMA_LP_FP8 = 0, MFMA_LP_MXFP8 = 1, MFMA_LP_MXFP4 = 2 };
+// MFMA_BF16 is the check of mfma_check.h, so that one list of formats serves mfma-check; it has no GEMM here
+enum MfmaLpFmt { MFMA_LP_FP8 = 0, MFMA_LP_MXFP8 = 1, MFMA_LP_MXFP4 = 2, MFMA_BF16 = 3 };
 
 typedef int lp_v4i __attribute__((ext_vector_type(4)));
 typedef int lp_v8i __attribute__((ext_vector_type(8)));
@@ -48,13 +51,6 @@ __host__ __device__ constexpr int mfma_lp_check_kmax(int f) { return f == MFMA_L
 //   bank row: conflict-free.
 __host__ __device__ constexpr int mfma_lp_pad(int f) { return f == MFMA_LP_FP8 ? 8 : 16; }
 __host__ __device__ constexpr int mfma_lp_ld(int f, int k) { return mfma_lp_row_bytes(f, k) + mfma_lp_pad(f); }
-
-inline const char* mfma_lp_name(int f) { return f == MFMA_LP_FP8 ? "fp8" : f == MFMA_LP_MXFP8 ? "mxfp8" : "mxfp4"; }
-inline int mfma_lp_fmt(const std::string& name) {
-  for (int f = MFMA_LP_FP8; f <= MFMA_LP_MXFP4; ++f)
-    if (name == mfma_lp_name(f)) return f;
-  throw std::invalid_argument("unknown low-precision dtype '" + name + "': expected fp8, mxfp8 or mxfp4");
-}
 
 // Place of the E8M0 byte of (32-wide K block b, row or column i) in an LDS scale table. Block b
 // belongs to K step b >> 1 and lane half b & 1; the bytes of four consecutive steps of one (half,
@@ -341,13 +337,48 @@ __global__ __launch_bounds__(256, 4) void mfma_check_lp_kernel(uint32_t seed, in
 }
 
 // ---------------------------------------------------------------------------- runners
+template <int F>
+inline void mfma_check_lp_launch(const MfmaCheckRun& run, int rounds, int flips, int dbg_block, float* dbg_a, float* dbg_b,
+                                 float* dbg_c) {
+  hipLaunchKernelGGL(mfma_check_lp_kernel<F>, dim3(run.blocks), dim3(256), 0, 0, run.seed, rounds, flips,
+                     run.flip_pos.as<const uint32_t>(), run.errors.as<unsigned long long>(), run.nrec.as<unsigned>(),
+                     run.recs.as<MfmaCheckRecord>(), dbg_block, dbg_a, dbg_b, dbg_c);
+}
+
+// What a format runs on: its name, its check (launch and K) and its GEMM kernel.
+struct MfmaFmtOps {
+  const char* name;
+  MfmaCheckRun::Kernel check;
+  int check_k;
+  void (*gemm)(const uint8_t*, const uint8_t*, const uint8_t*, const uint8_t*, float*, int, int, int);
+};
+
+// throws std::invalid_argument unless fmt is in [MFMA_LP_FP8, last]
+inline const MfmaFmtOps& mfma_fmt_ops(int fmt, int last = MFMA_BF16) {
+  static const MfmaFmtOps ops[] = {
+      {"fp8", mfma_check_lp_launch<MFMA_LP_FP8>, mfma_lp_check_kmax(MFMA_LP_FP8), mfma_gemm_lp_kernel<MFMA_LP_FP8>},
+      {"mxfp8", mfma_check_lp_launch<MFMA_LP_MXFP8>, mfma_lp_check_kmax(MFMA_LP_MXFP8), mfma_gemm_lp_kernel<MFMA_LP_MXFP8>},
+      {"mxfp4", mfma_check_lp_launch<MFMA_LP_MXFP4>, mfma_lp_check_kmax(MFMA_LP_MXFP4), mfma_gemm_lp_kernel<MFMA_LP_MXFP4>},
+      {"bf16", mfma_check_launch_bf16, MFMA_CHECK_KMAX, nullptr}};
+  if (fmt < MFMA_LP_FP8 || fmt > last) throw std::invalid_argument("unknown low-precision format");
+  return ops[fmt];
+}
+
+inline const char* mfma_lp_name(int f) { return mfma_fmt_ops(f).name; }
+// the format named `name` among fp8, mxfp8, mxfp4 and, with last = MFMA_BF16, bf16
+inline int mfma_lp_fmt(const std::string& name, int last = MFMA_LP_MXFP4) {
+  for (int f = MFMA_LP_FP8; f <= last; ++f)
+    if (name == mfma_lp_name(f)) return f;
+  throw std::invalid_argument("unknown low-precision dtype '" + name + "': expected fp8, mxfp8 or mxfp4");
+}
+
 // C[m x n] fp32 = A[m x k] * B[k x n] from format codes, one code per byte, row-major. fp8: e4m3fn
 // codes, no scales (a_scales and b_scales empty). mxfp8 / mxfp4: e4m3fn / e2m1 codes with E8M0 scales,
 // A's as [m x k/32] and B's as [k/32 x n]. Packs fp4 pairs, transposes B and A's scales for the kernel.
 inline std::vector<float> mfma_gemm_lp_host(int fmt, const std::vector<uint8_t>& a, const std::vector<uint8_t>& b,
                                             const std::vector<uint8_t>& a_scales, const std::vector<uint8_t>& b_scales, int m,
                                             int n, int k, int dev) {
-  if (fmt < MFMA_LP_FP8 || fmt > MFMA_LP_MXFP4) throw std::invalid_argument("unknown low-precision format");
+  const MfmaFmtOps& ops = mfma_fmt_ops(fmt, MFMA_LP_MXFP4);
   if (m <= 0 || n <= 0 || m % MFMA_TILE || n % MFMA_TILE)
     throw std::invalid_argument("M and N must be positive multiples of 64");
   const int kstep = mfma_lp_kstep(fmt);
@@ -381,68 +412,25 @@ inline std::vector<float> mfma_gemm_lp_host(int fmt, const std::vector<uint8_t>&
   for (size_t i = 0; i < static_cast<size_t>(m); ++i)
     for (size_t kb = 0; kb < kblocks; ++kb) sat[kb * m + i] = a_scales[i * kblocks + kb];
   AK_HIP(hipSetDevice(dev));
-  const size_t cn = static_cast<size_t>(m) * n;
-  DevBuf da(ai.size()), db(bi.size()), dsa(sat.size()), dsb(b_scales.size()), dc(cn * sizeof(float));
-  AK_HIP(hipMemcpy(da.p, ai.data(), ai.size(), hipMemcpyHostToDevice));
-  AK_HIP(hipMemcpy(db.p, bi.data(), bi.size(), hipMemcpyHostToDevice));
-  if (kblocks) {
-    AK_HIP(hipMemcpy(dsa.p, sat.data(), sat.size(), hipMemcpyHostToDevice));
-    AK_HIP(hipMemcpy(dsb.p, b_scales.data(), b_scales.size(), hipMemcpyHostToDevice));
-  }
-  auto launch = [&](auto kernel) {
-    hipLaunchKernelGGL(kernel, dim3(static_cast<unsigned>(tiles)), dim3(256), 0, 0, static_cast<const uint8_t*>(da.p),
-                       static_cast<const uint8_t*>(db.p), static_cast<const uint8_t*>(dsa.p),
-                       static_cast<const uint8_t*>(dsb.p), static_cast<float*>(dc.p), m, n, k);
-  };
-  if (fmt == MFMA_LP_FP8) launch(mfma_gemm_lp_kernel<MFMA_LP_FP8>);
-  else if (fmt == MFMA_LP_MXFP8) launch(mfma_gemm_lp_kernel<MFMA_LP_MXFP8>);
-  else launch(mfma_gemm_lp_kernel<MFMA_LP_MXFP4>);
+  DevBuf da(ai), db(bi), dsa(sat), dsb(b_scales), dc(static_cast<size_t>(m) * n * sizeof(float));
+  hipLaunchKernelGGL(ops.gemm, dim3(static_cast<unsigned>(tiles)), dim3(256), 0, 0, da.as<const uint8_t>(),
+                     db.as<const uint8_t>(), dsa.as<const uint8_t>(), dsb.as<const uint8_t>(), dc.as<float>(), m, n, k);
   AK_HIP(hipGetLastError());
-  std::vector<float> c(cn);
-  AK_HIP(hipMemcpy(c.data(), dc.p, cn * sizeof(float), hipMemcpyDeviceToHost));
-  return c;
+  return dc.download<float>();
 }
 
-// The buffers and flip positions of MfmaCheckRun with the launch of format fmt's check.
-struct MfmaCheckLpRun {
-  MfmaCheckRun base;  // its own k is unused here
-  int fmt, blocks, k;
-  DevBuf &errors, &nrec, &recs;
-  MfmaCheckLpRun(int fmt_, int dev, uint32_t seed)
-      : base(dev, seed, MFMA_CHECK_KMAX), fmt(fmt_), blocks(base.blocks), k(mfma_lp_check_kmax(fmt_)), errors(base.errors),
-        nrec(base.nrec), recs(base.recs) {}
-  void launch(int rounds, int flips, int dbg_block = -1, float* dbg_a = nullptr, float* dbg_b = nullptr,
-              float* dbg_c = nullptr) {
-    auto go = [&](auto kernel) {
-      hipLaunchKernelGGL(kernel, dim3(blocks), dim3(256), 0, 0, base.seed, rounds, flips,
-                         static_cast<const uint32_t*>(base.flip_pos.p), static_cast<unsigned long long*>(errors.p),
-                         static_cast<unsigned*>(nrec.p), static_cast<MfmaCheckRecord*>(recs.p), dbg_block, dbg_a, dbg_b,
-                         dbg_c);
-    };
-    if (fmt == MFMA_LP_FP8) go(mfma_check_lp_kernel<MFMA_LP_FP8>);
-    else if (fmt == MFMA_LP_MXFP8) go(mfma_check_lp_kernel<MFMA_LP_MXFP8>);
-    else go(mfma_check_lp_kernel<MFMA_LP_MXFP4>);
-    AK_HIP(hipGetLastError());
-  }
-};
-
-// run_mfma_check on format fmt: rounds > 0 is one launch of exactly that many rounds, otherwise
-// the run is calibrated to ~target_ms.
+// run_mfma_check on format fmt, bf16 included: rounds > 0 is one launch of exactly that many rounds,
+// otherwise the run is calibrated to ~target_ms.
 inline MfmaCheckResult run_mfma_check_lp(int fmt, int rounds, double target_ms, int dev, uint32_t seed = 0x5eedu,
                                          int flips = 0) {
-  if (fmt < MFMA_LP_FP8 || fmt > MFMA_LP_MXFP4) throw std::invalid_argument("unknown low-precision format");
-  if (flips < 0 || flips > MFMA_CHECK_MAX_FLIPS) throw std::invalid_argument("selftest flips must be in [0, 4096]");
-  AK_HIP(hipSetDevice(dev));
-  MfmaCheckLpRun run(fmt, dev, seed);
-  return mfma_check_drive(run, rounds, target_ms, flips);
+  const MfmaFmtOps& ops = mfma_fmt_ops(fmt);
+  return mfma_check_drive(ops.check, ops.check_k, rounds, target_ms, dev, seed, flips);
 }
 
 // A and B of one workgroup decoded to fp32 with the scales applied, and its round-0 C
 inline MfmaCheckTile mfma_check_lp_tile_host(int fmt, int block, uint32_t seed, int dev) {
-  if (fmt < MFMA_LP_FP8 || fmt > MFMA_LP_MXFP4) throw std::invalid_argument("unknown low-precision format");
-  AK_HIP(hipSetDevice(dev));
-  MfmaCheckLpRun run(fmt, dev, seed);
-  return mfma_check_fetch_tile(run, block);
+  const MfmaFmtOps& ops = mfma_fmt_ops(fmt);
+  return mfma_check_fetch_tile(ops.check, ops.check_k, block, seed, dev);
 }
 
 }  // namespace amdkube

@@ -2,14 +2,14 @@
 
   python native/build.py            # CPU-side pybind modules + pause (g++), HIP targets (hipcc, gfx950)
   python native/build.py --cpu-only # just the g++ targets (used by the CPU test tier)
-  python native/build.py --sanitize # also the ASan/UBSan host builds (pause, topo self-test, sampler)
+  python native/build.py --sanitize # also the ASan/UBSan host builds (pause, topo self-test, sampler, check_core self-test)
                                     # and the ThreadSanitizer build of the activity sampler
 
 Outputs: amdkube/_native/{_amdsmi,_topo,_kproto,_quantile,_hipops}.<ext> and amdkube/_native/bin/{pause,
-amdkube-nsexec,amdkube-logpump,sysfs-prefetch-selftest,rocm-vector-add,hsa-vector-add,hbm-probe,gpu-burn,mfma-check,cu-check,xgmi-probe[,topo-selftest-asan,
+amdkube-nsexec,amdkube-logpump,sysfs-prefetch-selftest,check-core-selftest,rocm-vector-add,hsa-vector-add,hbm-probe,gpu-burn,mfma-check,cu-check,xgmi-probe[,topo-selftest-asan,
 pause-asan,
 amdkube-nsexec-asan,amdkube-logpump-asan,
-seccomp-check-asan,sampler-selftest-{asan,tsan},sysfs-prefetch-selftest-{asan,tsan}]}.
+seccomp-check-asan,sampler-selftest-{asan,tsan},sysfs-prefetch-selftest-{asan,tsan},check-core-selftest-asan]}.
 Targets are rebuilt only when a source/header is newer than the output.
 """
 from __future__ import annotations
@@ -75,6 +75,9 @@ def targets(sanitize=False, cpu_only=False):
         # the KFD-topology prefetch of hsa-vector-add, checked on a fake tree through its own fopen
         (n(BIN, "sysfs-prefetch-selftest"), [n("native/sysfs_prefetch_selftest.cpp"), n("native/sysfs_prefetch.h")],
          ["g++", "-O2", "-std=c++17", "-Wall", n("native/sysfs_prefetch_selftest.cpp"), "-pthread", "-ldl", "-o", "{out}"]),
+        # the calibration, flip positions and list splitting of the GPU checks, against the loops they replaced
+        (n(BIN, "check-core-selftest"), [n("native/check_core_selftest.cpp"), n("kernels/check_core.h")],
+         ["g++", "-O2", "-std=c++17", "-Wall", n("native/check_core_selftest.cpp"), "-o", "{out}"]),
         (n(BIN, "cni", "amdkube-cni"), [n("native/cni_ipam.cpp")],
          ["g++", "-O2", "-std=c++17", n("native/cni_ipam.cpp"), "-o", "{out}"]),
         (n(BIN, "cni", "amdkube-bridge"), [n("native/cni_bridge.cpp")],
@@ -105,6 +108,8 @@ def targets(sanitize=False, cpu_only=False):
             (n(BIN, "sysfs-prefetch-selftest-tsan"), [n("native/sysfs_prefetch_selftest.cpp"), n("native/sysfs_prefetch.h")],
              ["g++", "-O1", "-std=c++17", "-fsanitize=thread", "-fno-omit-frame-pointer", "-g",
               n("native/sysfs_prefetch_selftest.cpp"), "-pthread", "-ldl", "-o", "{out}"]),
+            (n(BIN, "check-core-selftest-asan"), [n("native/check_core_selftest.cpp"), n("kernels/check_core.h")],
+             ["g++", "-O1", "-std=c++17", *san, n("native/check_core_selftest.cpp"), "-o", "{out}"]),
             (n(BIN, "sampler-selftest-tsan"), [n("native/sampler_selftest.cpp"), n("native/sampler_core.h")],
              ["g++", "-O1", "-std=c++17", "-fsanitize=thread", "-fno-omit-frame-pointer", "-g",
               n("native/sampler_selftest.cpp"), "-pthread", "-o", "{out}"]),
@@ -114,14 +119,15 @@ def targets(sanitize=False, cpu_only=False):
         if hip is None:
             raise SystemExit("hipcc not found: cannot build gfx950 targets")
         ho = [hip, f"--offload-arch={ARCH}", "-O3", "-std=c++17"]
-        hdr = n("kernels/gpu_common.h")
-        chk = n("kernels/mfma_check.h")      # included by gpu_common.h
-        lp = n("kernels/mfma_check_lp.h")    # included by gpu_common.h
-        cu = n("kernels/cu_check.h")         # included by gpu_common.h
+        # each header with what it includes: a program depends on what it launches
+        base = [n("kernels/gpu_common.h"), n("kernels/gpu_host.h"), n("kernels/check_core.h")]
+        chk = [n("kernels/mfma_check.h"), *base]
+        lp = [n("kernels/mfma_check_lp.h"), *chk]
+        cu = [n("kernels/cu_check.h"), *base]
         t += [
-            (n(OUT, "_hipops" + EXT), [n("native/hipops.hip"), hdr, chk, lp, cu],
+            (n(OUT, "_hipops" + EXT), [n("native/hipops.hip"), n("kernels/cu_check.h"), *lp],
              [*ho, "-shared", "-fPIC", *py, n("native/hipops.hip"), "-o", "{out}"]),
-            (n(BIN, "rocm-vector-add"), [n("kernels/vector_add.hip"), hdr, chk, lp, cu], [*ho, n("kernels/vector_add.hip"), "-o", "{out}"]),
+            (n(BIN, "rocm-vector-add"), [n("kernels/vector_add.hip"), *base], [*ho, n("kernels/vector_add.hip"), "-o", "{out}"]),
             # the HIP-free pod workload: a bare gfx950 code object, then the HSA host embedding it
             (n(BIN, "hsa-vector-add"), [n("kernels/hsa_vector_add.cpp"), n("kernels/vadd_kernel.hip"),
                                         n("native/sysfs_prefetch.h")],
@@ -130,12 +136,10 @@ def targets(sanitize=False, cpu_only=False):
               f'g++ -O2 -std=c++17 -Wall -DVADD_CO_PATH=\\"{n(OUT, "lib", "vadd_" + ARCH + ".co")}\\" '
               f'-I{ROCM}/include {n("kernels/hsa_vector_add.cpp")} -L{ROCM}/lib -Wl,-rpath,{ROCM}/lib -lhsa-runtime64 -pthread -ldl -o "$1"',
               hip, "{out}"]),
-            (n(BIN, "hbm-probe"), [n("kernels/hbm_probe.hip"), hdr, chk, lp, cu], [*ho, n("kernels/hbm_probe.hip"), "-o", "{out}"]),
-            (n(BIN, "gpu-burn"), [n("kernels/gpu_burn.hip"), hdr, chk, lp, cu], [*ho, n("kernels/gpu_burn.hip"), "-o", "{out}"]),
-            (n(BIN, "mfma-check"), [n("kernels/mfma_check.hip"), hdr, chk, lp, cu],
-             [*ho, n("kernels/mfma_check.hip"), "-o", "{out}"]),
-            (n(BIN, "cu-check"), [n("kernels/cu_check.hip"), hdr, chk, lp, cu],
-             [*ho, n("kernels/cu_check.hip"), "-o", "{out}"]),
+            (n(BIN, "hbm-probe"), [n("kernels/hbm_probe.hip"), *base], [*ho, n("kernels/hbm_probe.hip"), "-o", "{out}"]),
+            (n(BIN, "gpu-burn"), [n("kernels/gpu_burn.hip"), *chk], [*ho, n("kernels/gpu_burn.hip"), "-o", "{out}"]),
+            (n(BIN, "mfma-check"), [n("kernels/mfma_check.hip"), *lp], [*ho, n("kernels/mfma_check.hip"), "-o", "{out}"]),
+            (n(BIN, "cu-check"), [n("kernels/cu_check.hip"), *cu], [*ho, n("kernels/cu_check.hip"), "-o", "{out}"]),
             (n(BIN, "xgmi-probe"), [n("kernels/xgmi_probe.cpp")],
              [*ho, "-x", "hip", n("kernels/xgmi_probe.cpp"), *rocm_inc, *rpath, "-lrccl", "-o", "{out}"]),
         ]

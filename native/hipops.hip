@@ -2,12 +2,13 @@
 //
 // The AMD device plugin uses these as its health probe (HBM pattern check before a GPU
 // is advertised Healthy) and the GPU test tier uses them to check the kernels against a
-// host fp32 reference. Kernels live in kernels/gpu_common.h (shared with the pod binaries).
+// host fp32 reference. Kernels live in kernels/ (gpu_common.h and the check headers, shared with the pod binaries).
 #include <pybind11/numpy.h>
 #include <pybind11/pybind11.h>
 #include <pybind11/stl.h>
 
-#include "../kernels/gpu_common.h"
+#include "../kernels/cu_check.h"
+#include "../kernels/mfma_check_lp.h"
 
 namespace py = pybind11;
 
@@ -36,8 +37,6 @@ static py::dict check_result(const amdkube::MfmaCheckResult& r, const char* rate
   return o;
 }
 
-static const char* const kCuUnits[3] = {"lds", "valu", "trans"};
-
 static py::dict cu_location(const amdkube::CuLocation& l) {
   py::dict d;
   d["xcc"] = l.xcc;
@@ -52,8 +51,8 @@ static py::dict cu_check_result(const amdkube::CuCheckResult& r) {
   py::dict o, by_unit;
   py::list units, locations, bad, recs;
   for (int u = 0; u < 3; ++u) {
-    if (r.units & (1 << u)) units.append(kCuUnits[u]);
-    by_unit[kCuUnits[u]] = r.errors_by_unit[u];
+    if (r.units & (1 << u)) units.append(amdkube::CU_UNIT_NAMES[u]);
+    by_unit[amdkube::CU_UNIT_NAMES[u]] = r.errors_by_unit[u];
   }
   for (const amdkube::CuLocation& l : r.locations) locations.append(cu_location(l));
   for (const amdkube::CuCheckBadCu& b : r.bad_cus) {
@@ -63,7 +62,7 @@ static py::dict cu_check_result(const amdkube::CuCheckResult& r) {
   }
   for (const amdkube::CuCheckRecord& e : r.first_errors) {
     py::dict d = cu_location(amdkube::cu_decode_location(e.hw_id, e.xcc_id));
-    d["unit"] = kCuUnits[e.unit < 3 ? e.unit : 0];
+    d["unit"] = amdkube::CU_UNIT_NAMES[e.unit < 3 ? e.unit : 0];
     d["block"] = e.block;
     d["round"] = e.round;
     d["pass"] = e.pass;
@@ -93,8 +92,27 @@ static py::dict cu_check_result(const amdkube::CuCheckResult& r) {
   return o;
 }
 
-using bytes_in = py::array_t<uint8_t, py::array::c_style | py::array::forcecast>;
-static std::vector<uint8_t> to_vec(const bytes_in& x) { return std::vector<uint8_t>(x.data(), x.data() + x.size()); }
+template <class T>
+using array_in = py::array_t<T, py::array::c_style | py::array::forcecast>;
+using bytes_in = array_in<uint8_t>;
+template <class T>
+static std::vector<T> to_vec(const array_in<T>& x) {
+  return std::vector<T>(x.data(), x.data() + x.size());
+}
+
+// fn() with the GIL released
+template <class F>
+static auto nogil(F&& fn) {
+  py::gil_scoped_release release;
+  return fn();
+}
+
+// (A, B, C) of one workgroup of a matrix-core check
+static py::tuple tile_tuple(const amdkube::MfmaCheckTile& t) {
+  return py::make_tuple(py::array_t<float>({amdkube::MFMA_TILE, t.k}, t.a.data()),
+                        py::array_t<float>({t.k, amdkube::MFMA_TILE}, t.b.data()),
+                        py::array_t<float>({amdkube::MFMA_TILE, amdkube::MFMA_TILE}, t.c.data()));
+}
 
 PYBIND11_MODULE(_hipops, m) {
   m.doc() = "amdkube HIP (gfx950) validation kernels: vector add, HBM probe, MFMA burn, MFMA check, CU check";
@@ -121,11 +139,7 @@ PYBIND11_MODULE(_hipops, m) {
   m.def(
       "vector_add",
       [](size_t n, int dev) {
-        amdkube::VaddResult r;
-        {
-          py::gil_scoped_release nogil;
-          r = amdkube::run_vector_add(n, dev);
-        }
+        const amdkube::VaddResult r = nogil([&] { return amdkube::run_vector_add(n, dev); });
         py::dict o;
         o["ok"] = r.ok;
         o["kernel_ms"] = r.kernel_ms;
@@ -136,11 +150,7 @@ PYBIND11_MODULE(_hipops, m) {
   m.def(
       "hbm_probe",
       [](size_t mib, int iters, int dev) {
-        amdkube::HbmResult r;
-        {
-          py::gil_scoped_release nogil;
-          r = amdkube::run_hbm_probe(mib << 20, iters, dev);
-        }
+        const amdkube::HbmResult r = nogil([&] { return amdkube::run_hbm_probe(mib << 20, iters, dev); });
         py::dict o;
         o["bytes"] = r.bytes;
         o["iters"] = r.iters;
@@ -155,95 +165,61 @@ PYBIND11_MODULE(_hipops, m) {
   // caller-supplied data (numpy arrays, e.g. torch.Tensor.numpy()) → the same kernels
   m.def(
       "vector_add_arrays",
-      [](py::array_t<float, py::array::c_style | py::array::forcecast> a,
-         py::array_t<float, py::array::c_style | py::array::forcecast> b, int dev) {
-        std::vector<float> va(a.data(), a.data() + a.size()), vb(b.data(), b.data() + b.size()), vc;
-        {
-          py::gil_scoped_release nogil;
-          vc = amdkube::vector_add_host(va, vb, dev);
-        }
+      [](array_in<float> a, array_in<float> b, int dev) {
+        const std::vector<float> va = to_vec(a), vb = to_vec(b);
+        const std::vector<float> vc = nogil([&] { return amdkube::vector_add_host(va, vb, dev); });
         return py::array_t<float>(vc.size(), vc.data());
       },
       py::arg("a"), py::arg("b"), py::arg("device") = 0);
   m.def(
       "hbm_pattern",
       [](size_t n16, uint32_t seed, int dev) {
-        std::vector<uint32_t> w;
-        {
-          py::gil_scoped_release nogil;
-          w = amdkube::hbm_pattern_host(n16, seed, dev);
-        }
+        const std::vector<uint32_t> w = nogil([&] { return amdkube::hbm_pattern_host(n16, seed, dev); });
         return py::array_t<uint32_t>(w.size(), w.data());
       },
       py::arg("n16"), py::arg("seed") = 0x5eedu, py::arg("device") = 0);
   m.def(
       "hbm_verify_words",
-      [](py::array_t<uint32_t, py::array::c_style | py::array::forcecast> words, uint32_t seed, int dev) {
-        std::vector<uint32_t> w(words.data(), words.data() + words.size());
-        py::gil_scoped_release nogil;
-        return amdkube::hbm_verify_host(w, seed, dev);
+      [](array_in<uint32_t> words, uint32_t seed, int dev) {
+        const std::vector<uint32_t> w = to_vec(words);
+        return nogil([&] { return amdkube::hbm_verify_host(w, seed, dev); });
       },
       py::arg("words"), py::arg("seed") = 0x5eedu, py::arg("device") = 0);
   m.def(
       "hbm_copy_words",
-      [](py::array_t<uint32_t, py::array::c_style | py::array::forcecast> words, int dev) {
-        std::vector<uint32_t> w(words.data(), words.data() + words.size()), o;
-        {
-          py::gil_scoped_release nogil;
-          o = amdkube::hbm_copy_host(w, dev);
-        }
+      [](array_in<uint32_t> words, int dev) {
+        const std::vector<uint32_t> w = to_vec(words);
+        const std::vector<uint32_t> o = nogil([&] { return amdkube::hbm_copy_host(w, dev); });
         return py::array_t<uint32_t>(o.size(), o.data());
       },
       py::arg("words"), py::arg("device") = 0);
   m.def(
       "mfma_tile",
-      [](py::array_t<uint16_t, py::array::c_style | py::array::forcecast> a_bits,
-         py::array_t<uint16_t, py::array::c_style | py::array::forcecast> b_bits, int k, int dev) {
-        std::vector<uint16_t> a(a_bits.data(), a_bits.data() + a_bits.size()), b(b_bits.data(), b_bits.data() + b_bits.size());
-        std::vector<float> c;
-        {
-          py::gil_scoped_release nogil;
-          c = amdkube::mfma_tile_host(a, b, k, dev);
-        }
+      [](array_in<uint16_t> a_bits, array_in<uint16_t> b_bits, int k, int dev) {
+        const std::vector<uint16_t> a = to_vec(a_bits), b = to_vec(b_bits);
+        const std::vector<float> c = nogil([&] { return amdkube::mfma_tile_host(a, b, k, dev); });
         return py::array_t<float>({32, 32}, c.data());
       },
       py::arg("a_bits"), py::arg("b_bits"), py::arg("k"), py::arg("device") = 0);
   m.def(
       "mfma_gemm",
-      [](py::array_t<uint16_t, py::array::c_style | py::array::forcecast> a_bits,
-         py::array_t<uint16_t, py::array::c_style | py::array::forcecast> b_bits, int mm, int nn, int k, int dev) {
-        std::vector<uint16_t> a(a_bits.data(), a_bits.data() + a_bits.size()), b(b_bits.data(), b_bits.data() + b_bits.size());
-        std::vector<float> c;
-        {
-          py::gil_scoped_release nogil;
-          c = amdkube::mfma_gemm_host(a, b, mm, nn, k, dev);
-        }
+      [](array_in<uint16_t> a_bits, array_in<uint16_t> b_bits, int mm, int nn, int k, int dev) {
+        const std::vector<uint16_t> a = to_vec(a_bits), b = to_vec(b_bits);
+        const std::vector<float> c = nogil([&] { return amdkube::mfma_gemm_host(a, b, mm, nn, k, dev); });
         return py::array_t<float>({mm, nn}, c.data());
       },
       py::arg("a_bits"), py::arg("b_bits"), py::arg("m"), py::arg("n"), py::arg("k"), py::arg("device") = 0);
   m.def(
       "mfma_check",
       [](int rounds, double ms, int dev, uint32_t seed, int flips) {
-        amdkube::MfmaCheckResult r;
-        {
-          py::gil_scoped_release nogil;
-          r = amdkube::run_mfma_check(rounds, ms, dev, seed, flips);
-        }
-        return check_result(r, "bf16_tflops");
+        return check_result(nogil([&] { return amdkube::run_mfma_check(rounds, ms, dev, seed, flips); }), "bf16_tflops");
       },
       py::arg("rounds") = 0, py::arg("ms") = 50.0, py::arg("device") = 0, py::arg("seed") = 0x5eedu,
       py::arg("selftest_flips") = 0);
   m.def(
       "mfma_check_tile",
       [](int block, uint32_t seed, int dev) {
-        amdkube::MfmaCheckTile t;
-        {
-          py::gil_scoped_release nogil;
-          t = amdkube::mfma_check_tile_host(block, seed, dev);
-        }
-        return py::make_tuple(py::array_t<float>({amdkube::MFMA_TILE, t.k}, t.a.data()),
-                              py::array_t<float>({t.k, amdkube::MFMA_TILE}, t.b.data()),
-                              py::array_t<float>({amdkube::MFMA_TILE, amdkube::MFMA_TILE}, t.c.data()));
+        return tile_tuple(nogil([&] { return amdkube::mfma_check_tile_host(block, seed, dev); }));
       },
       py::arg("block"), py::arg("seed") = 0x5eedu, py::arg("device") = 0);
   // the low-precision matrix-core paths (kernels/mfma_check_lp.h): dtype is fp8, mxfp8 or mxfp4
@@ -252,12 +228,8 @@ PYBIND11_MODULE(_hipops, m) {
       [](const std::string& dtype, bytes_in a_codes, bytes_in b_codes, bytes_in a_scales, bytes_in b_scales, int mm, int nn,
          int k, int dev) {
         const int fmt = amdkube::mfma_lp_fmt(dtype);
-        std::vector<uint8_t> a = to_vec(a_codes), b = to_vec(b_codes), sa = to_vec(a_scales), sb = to_vec(b_scales);
-        std::vector<float> c;
-        {
-          py::gil_scoped_release nogil;
-          c = amdkube::mfma_gemm_lp_host(fmt, a, b, sa, sb, mm, nn, k, dev);
-        }
+        const std::vector<uint8_t> a = to_vec(a_codes), b = to_vec(b_codes), sa = to_vec(a_scales), sb = to_vec(b_scales);
+        const std::vector<float> c = nogil([&] { return amdkube::mfma_gemm_lp_host(fmt, a, b, sa, sb, mm, nn, k, dev); });
         return py::array_t<float>({mm, nn}, c.data());
       },
       py::arg("dtype"), py::arg("a_codes"), py::arg("b_codes"), py::arg("a_scales"), py::arg("b_scales"), py::arg("m"),
@@ -266,12 +238,7 @@ PYBIND11_MODULE(_hipops, m) {
       "mfma_check_lp",
       [](const std::string& dtype, int rounds, double ms, int dev, uint32_t seed, int flips) {
         const int fmt = amdkube::mfma_lp_fmt(dtype);
-        amdkube::MfmaCheckResult r;
-        {
-          py::gil_scoped_release nogil;
-          r = amdkube::run_mfma_check_lp(fmt, rounds, ms, dev, seed, flips);
-        }
-        py::dict o = check_result(r, "tflops");
+        py::dict o = check_result(nogil([&] { return amdkube::run_mfma_check_lp(fmt, rounds, ms, dev, seed, flips); }), "tflops");
         o["dtype"] = dtype;
         return o;
       },
@@ -281,37 +248,21 @@ PYBIND11_MODULE(_hipops, m) {
       "mfma_check_lp_tile",
       [](const std::string& dtype, int block, uint32_t seed, int dev) {
         const int fmt = amdkube::mfma_lp_fmt(dtype);
-        amdkube::MfmaCheckTile t;
-        {
-          py::gil_scoped_release nogil;
-          t = amdkube::mfma_check_lp_tile_host(fmt, block, seed, dev);
-        }
-        return py::make_tuple(py::array_t<float>({amdkube::MFMA_TILE, t.k}, t.a.data()),
-                              py::array_t<float>({t.k, amdkube::MFMA_TILE}, t.b.data()),
-                              py::array_t<float>({amdkube::MFMA_TILE, amdkube::MFMA_TILE}, t.c.data()));
+        return tile_tuple(nogil([&] { return amdkube::mfma_check_lp_tile_host(fmt, block, seed, dev); }));
       },
       py::arg("dtype"), py::arg("block"), py::arg("seed") = 0x5eedu, py::arg("device") = 0);
   // the per-CU check (kernels/cu_check.h): units is a mask over lds = 1, valu = 2, trans = 4
   m.def(
       "cu_check",
       [](int rounds, double ms, int dev, uint32_t seed, int flips, int units) {
-        amdkube::CuCheckResult r;
-        {
-          py::gil_scoped_release nogil;
-          r = amdkube::run_cu_check(rounds, ms, dev, seed, flips, units);
-        }
-        return cu_check_result(r);
+        return cu_check_result(nogil([&] { return amdkube::run_cu_check(rounds, ms, dev, seed, flips, units); }));
       },
       py::arg("rounds") = 0, py::arg("ms") = 50.0, py::arg("device") = 0, py::arg("seed") = 0x5eedu,
       py::arg("selftest_flips") = 0, py::arg("units") = 7);
   m.def(
       "cu_check_dump",
       [](int block, uint32_t seed, int dev) {
-        amdkube::CuCheckDump d;
-        {
-          py::gil_scoped_release nogil;
-          d = amdkube::cu_check_dump_host(block, seed, dev);
-        }
+        const amdkube::CuCheckDump d = nogil([&] { return amdkube::cu_check_dump_host(block, seed, dev); });
         const py::ssize_t T = amdkube::CU_CHECK_THREADS;
         py::dict o;
         o["hw_id"] = d.hw_id;
@@ -331,11 +282,7 @@ PYBIND11_MODULE(_hipops, m) {
   m.def(
       "mfma_burn",
       [](double ms, int dev) {
-        amdkube::BurnResult r;
-        {
-          py::gil_scoped_release nogil;
-          r = amdkube::run_mfma_burn(ms, dev);
-        }
+        const amdkube::BurnResult r = nogil([&] { return amdkube::run_mfma_burn(ms, dev); });
         py::dict o;
         o["ms"] = r.ms;
         o["iters"] = r.iters;

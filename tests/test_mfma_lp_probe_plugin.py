@@ -1,7 +1,5 @@
 """Device-plugin side of the low-precision matrix-core probe: `mfma-lp` in `health_probe`, run
 against stub probe binaries that log their arguments, on the fake backend (CPU tier)."""
-import stat
-
 import pytest
 
 from amdkube.deviceplugin import amd
@@ -9,42 +7,14 @@ from amdkube.smi import FakeBackend, device_id
 from amdkube.smi.backend import visibility_token
 from amdkube.smi.health import HEALTH_REASON_ATTR
 from tests.conftest import run
+from tests.probe_stubs import make_stubs, start as _start
 
-# logs `<name> <token> <arguments>`; `fail_args` is a substring of the arguments of the run that exits 1
-STUB = """#!/bin/sh
-echo "{name} $ROCR_VISIBLE_DEVICES $@" >> "{log}"
-echo '{{"errors":3}}'
-case "{name} $@" in *"{fail_args}"*) if [ -n "{fail_args}" ] && [ "$ROCR_VISIBLE_DEVICES" = "{fail_token}" ]; then exit 1; fi;; esac
-exit 0
-"""
 LP_ARGS = "--dtype fp8,mxfp8,mxfp4 --ms 200"
 
 
 @pytest.fixture
 def stubs(short_tmp, monkeypatch):
-    bindir = short_tmp / "bin"
-    bindir.mkdir()
-    log = short_tmp / "probe.log"
-    monkeypatch.setattr(amd, "BIN_DIR", str(bindir))
-
-    def make(fail_args="", fail_token=""):
-        for name in ("hbm-probe", "mfma-check"):
-            p = bindir / name
-            p.write_text(STUB.format(name=name, log=log, fail_args=fail_args, fail_token=fail_token))
-            p.chmod(p.stat().st_mode | stat.S_IXUSR)
-
-    def calls():
-        """[(binary, token, arguments)]"""
-        return [tuple(line.split(" ", 2)) for line in log.read_text().splitlines()] if log.exists() else []
-    return make, calls
-
-
-def _start(fb, tmp, probe, **kw):
-    async def go():
-        p = amd.AMDGPUPlugin(fb, plugins_dir=str(tmp / "plugins"), health_interval=3600.0, health_probe=probe, **kw)
-        await p.start()
-        return p
-    return go()
+    return make_stubs(short_tmp, monkeypatch, fields=3)
 
 
 def test_the_probe_table_keeps_its_order_and_gains_mfma_lp():

@@ -1,7 +1,6 @@
 """Device-plugin side of the matrix-core health probe: `health_probe` as a comma list over hbm and
 mfma, run against stub probe binaries on the fake backend (CPU tier)."""
 import os
-import stat
 
 import pytest
 
@@ -10,41 +9,12 @@ from amdkube.smi import FakeBackend, device_id
 from amdkube.smi.backend import visibility_token
 from amdkube.smi.health import HEALTH_REASON_ATTR, request_reset
 from tests.conftest import run
-
-STUB = """#!/bin/sh
-echo "{name} $ROCR_VISIBLE_DEVICES" >> "{log}"
-echo '{{"errors":3}}'
-if [ "{name}" = "{fail_name}" ] && [ "$ROCR_VISIBLE_DEVICES" = "{fail_token}" ]; then exit 1; fi
-exit 0
-"""
+from tests.probe_stubs import make_stubs, start as _start
 
 
 @pytest.fixture
 def stubs(short_tmp, monkeypatch):
-    """BIN_DIR → a directory of stub hbm-probe / mfma-check scripts that log `<name> <token>` per run;
-    make(fail_name, fail_token) writes them so that one probe exits 1 for one GPU's token."""
-    bindir = short_tmp / "bin"
-    bindir.mkdir()
-    log = short_tmp / "probe.log"
-    monkeypatch.setattr(amd, "BIN_DIR", str(bindir))
-
-    def make(fail_name="", fail_token=""):
-        for name in ("hbm-probe", "mfma-check"):
-            p = bindir / name
-            p.write_text(STUB.format(name=name, log=log, fail_name=fail_name, fail_token=fail_token))
-            p.chmod(p.stat().st_mode | stat.S_IXUSR)
-
-    def calls():
-        return [tuple(line.split(" ", 1)) for line in log.read_text().splitlines()] if log.exists() else []
-    return make, calls
-
-
-def _start(fb, tmp, probe, **kw):
-    async def go():
-        p = amd.AMDGPUPlugin(fb, plugins_dir=str(tmp / "plugins"), health_interval=3600.0, health_probe=probe, **kw)
-        await p.start()
-        return p
-    return go()
+    return make_stubs(short_tmp, monkeypatch, fields=2)
 
 
 def test_mfma_probe_marks_the_failing_gpu_and_a_reset_clears_it(short_tmp, stubs):
