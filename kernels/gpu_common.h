@@ -22,8 +22,10 @@
 //   CU check     (cu_check.h) one workgroup per CU with all 160 KiB of LDS: a march over the LDS, the
 //                same multiply-adds on the fp32, packed-fp32, fp64 and integer pipes, the
 //                transcendental unit on two waves, and the XCD / shader engine / CU it ran on
-// The host side is shared: gpu_host.h (AK_HIP, DevInfo, DevBuf, GpuTimer) and check_core.h (calibration,
-// self-test flip positions, list splitting; plain C++, self-tested on the CPU).
+// The host side is shared: gpu_host.h (AK_HIP, DevInfo, DevBuf, GpuTimer), check_core.h (calibration,
+// self-test flip positions, list splitting) and vadd_contract.h (the pod workload's contract, which
+// hsa-vector-add shares: flags, inputs, verification, stream_grid, output lines, exit codes); the last
+// two are plain C++, self-tested on the CPU.
 //
 // Every launch is bounded by construction (grid-stride loops over checked sizes) and uses
 // no inter-workgroup synchronisation, so no launch can hang the device.
@@ -31,18 +33,18 @@
 
 #include "check_core.h"
 #include "gpu_host.h"
+#include "vadd_contract.h"
 
 namespace amdkube {
 
 // ---------------------------------------------------------------------------- kernels
 // Each workgroup owns one contiguous chunk of the float4 range (streaming, non-temporal): on
 // MI355X the chunked layout at 64 WG/CU moves 5.95 TB/s of a+b->c traffic against 5.46 TB/s for
-// the grid-stride loop (hack/exp/write_sweep.hip, 3 x 1 GiB).
-constexpr int VADD_BLOCKS_PER_CU = 64;
+// the grid-stride loop (hack/exp/write_sweep.hip, 3 x 1 GiB): VADD_BLOCKS_PER_CU (vadd_contract.h).
 typedef float v4f __attribute__((ext_vector_type(4)));
 
-__global__ __launch_bounds__(256) void vadd_kernel(const float* __restrict__ a, const float* __restrict__ b,
-                                                   float* __restrict__ c, size_t n) {
+__global__ __launch_bounds__(VADD_WG) void vadd_kernel(const float* __restrict__ a, const float* __restrict__ b,
+                                                       float* __restrict__ c, size_t n) {
   const size_t n4 = n >> 2;
   const v4f* a4 = reinterpret_cast<const v4f*>(a);
   const v4f* b4 = reinterpret_cast<const v4f*>(b);
@@ -232,13 +234,7 @@ __global__ __launch_bounds__(64) void mfma_tile_kernel(const __bf16* __restrict_
 }
 
 // ---------------------------------------------------------------------------- runners
-inline int stream_grid(size_t items, int cu_count, int per_cu = 8) {
-  size_t want = (items + 255) / 256;
-  size_t cap = static_cast<size_t>(cu_count > 0 ? cu_count : 256) * per_cu;
-  if (want < 1) want = 1;
-  return static_cast<int>(want < cap ? want : cap);
-}
-
+// (stream_grid, the pod workload's inputs and its verification: vadd_contract.h)
 struct VaddResult {
   bool ok = false;
   double kernel_ms = 0;
@@ -251,25 +247,16 @@ inline VaddResult run_vector_add(size_t n, int dev) {
   AK_HIP(hipSetDevice(dev));
   DevInfo info = dev_info(dev);
   std::vector<float> ha(n), hb(n);
-  uint32_t s = 12345u;
-  for (size_t i = 0; i < n; ++i) {
-    s = s * 1664525u + 1013904223u;
-    ha[i] = static_cast<float>(s >> 8) / 16777216.0f;
-    s = s * 1664525u + 1013904223u;
-    hb[i] = static_cast<float>(s >> 8) / 16777216.0f;
-  }
+  vadd_fill_inputs(ha.data(), hb.data(), n);
   DevBuf da(ha), db(hb), dc(n * sizeof(float));
   GpuTimer timer;
   const int grid = stream_grid((n + 3) / 4, info.cu_count, VADD_BLOCKS_PER_CU);
   r.kernel_ms = timer.time([&] {
-    hipLaunchKernelGGL(vadd_kernel, dim3(grid), dim3(256), 0, 0, da.as<float>(), db.as<float>(), dc.as<float>(), n);
+    hipLaunchKernelGGL(vadd_kernel, dim3(grid), dim3(VADD_WG), 0, 0, da.as<float>(), db.as<float>(), dc.as<float>(), n);
     AK_HIP(hipGetLastError());
   });
   const std::vector<float> hc = dc.download<float>();
-  for (size_t i = 0; i < n; ++i) {
-    float d = hc[i] - (ha[i] + hb[i]);
-    if (d > 1e-5f || d < -1e-5f) ++r.mismatches;
-  }
+  r.mismatches = vadd_count_mismatches(ha.data(), hb.data(), hc.data(), n);
   r.ok = r.mismatches == 0;
   return r;
 }
@@ -282,7 +269,7 @@ inline std::vector<float> vector_add_host(const std::vector<float>& a, const std
   const size_t n = a.size();
   DevBuf da(a), db(b), dc(n * sizeof(float));
   const int grid = stream_grid((n + 3) / 4, dev_info(dev).cu_count, VADD_BLOCKS_PER_CU);
-  hipLaunchKernelGGL(vadd_kernel, dim3(grid), dim3(256), 0, 0, da.as<const float>(), db.as<const float>(), dc.as<float>(), n);
+  hipLaunchKernelGGL(vadd_kernel, dim3(grid), dim3(VADD_WG), 0, 0, da.as<const float>(), db.as<const float>(), dc.as<float>(), n);
   AK_HIP(hipGetLastError());
   return dc.download<float>();
 }

@@ -2,14 +2,17 @@
 
   python native/build.py            # CPU-side pybind modules + pause (g++), HIP targets (hipcc, gfx950)
   python native/build.py --cpu-only # just the g++ targets (used by the CPU test tier)
-  python native/build.py --sanitize # also the ASan/UBSan host builds (pause, topo self-test, sampler, check_core self-test)
-                                    # and the ThreadSanitizer build of the activity sampler
+  python native/build.py --sanitize # also the ASan/UBSan host builds (pause, topo self-test, sampler, and the check_core,
+                                    # vadd_contract and io_trace self-tests) and the ThreadSanitizer builds of the
+                                    # activity sampler, the prefetch and the I/O trace
 
 Outputs: amdkube/_native/{_amdsmi,_topo,_kproto,_quantile,_hipops}.<ext> and amdkube/_native/bin/{pause,
-amdkube-nsexec,amdkube-logpump,sysfs-prefetch-selftest,check-core-selftest,rocm-vector-add,hsa-vector-add,hbm-probe,gpu-burn,mfma-check,cu-check,xgmi-probe[,topo-selftest-asan,
+amdkube-nsexec,amdkube-logpump,sysfs-prefetch-selftest,check-core-selftest,vadd-contract-selftest,io-trace-selftest,
+rocm-vector-add,hsa-vector-add,hbm-probe,gpu-burn,mfma-check,cu-check,xgmi-probe[,topo-selftest-asan,
 pause-asan,
 amdkube-nsexec-asan,amdkube-logpump-asan,
-seccomp-check-asan,sampler-selftest-{asan,tsan},sysfs-prefetch-selftest-{asan,tsan},check-core-selftest-asan]}.
+seccomp-check-asan,sampler-selftest-{asan,tsan},sysfs-prefetch-selftest-{asan,tsan},check-core-selftest-asan,
+vadd-contract-selftest-asan,io-trace-selftest-{asan,tsan}]}.
 Targets are rebuilt only when a source/header is newer than the output.
 """
 from __future__ import annotations
@@ -45,6 +48,8 @@ def targets(sanitize=False, cpu_only=False):
     rocm_inc = [f"-I{ROCM}/include"]
     rpath = [f"-L{ROCM}/lib", f"-Wl,-rpath,{ROCM}/lib"]
     n = lambda *p: os.path.join(ROOT, *p)  # noqa: E731
+    vadd_selftest = [n("native/vadd_contract_selftest.cpp"), n("kernels/vadd_contract.h")]
+    trace_selftest = [n("native/io_trace_selftest.cpp"), n("native/io_trace.h"), n("native/sysfs_prefetch.h")]
     t = [
         (n(OUT, "_topo" + EXT), [n("native/topo_alloc.cpp"), n("native/topo_core.h")],
          ["g++", "-O3", "-std=c++17", "-shared", "-fPIC", *py, n("native/topo_alloc.cpp"), "-o", "{out}"]),
@@ -78,6 +83,11 @@ def targets(sanitize=False, cpu_only=False):
         # the calibration, flip positions and list splitting of the GPU checks, against the loops they replaced
         (n(BIN, "check-core-selftest"), [n("native/check_core_selftest.cpp"), n("kernels/check_core.h")],
          ["g++", "-O2", "-std=c++17", "-Wall", n("native/check_core_selftest.cpp"), "-o", "{out}"]),
+        # the pod workload's contract (flags, inputs, verification, grid, output lines) against the two copies it replaced
+        (n(BIN, "vadd-contract-selftest"), vadd_selftest, ["g++", "-O2", "-std=c++17", "-Wall", vadd_selftest[0], "-o", "{out}"]),
+        # the I/O trace of hsa-vector-add through the program's own fopen / fclose / open / opendir
+        (n(BIN, "io-trace-selftest"), trace_selftest,
+         ["g++", "-O2", "-std=c++17", "-Wall", trace_selftest[0], "-pthread", "-ldl", "-o", "{out}"]),
         (n(BIN, "cni", "amdkube-cni"), [n("native/cni_ipam.cpp")],
          ["g++", "-O2", "-std=c++17", n("native/cni_ipam.cpp"), "-o", "{out}"]),
         (n(BIN, "cni", "amdkube-bridge"), [n("native/cni_bridge.cpp")],
@@ -110,6 +120,13 @@ def targets(sanitize=False, cpu_only=False):
               n("native/sysfs_prefetch_selftest.cpp"), "-pthread", "-ldl", "-o", "{out}"]),
             (n(BIN, "check-core-selftest-asan"), [n("native/check_core_selftest.cpp"), n("kernels/check_core.h")],
              ["g++", "-O1", "-std=c++17", *san, n("native/check_core_selftest.cpp"), "-o", "{out}"]),
+            (n(BIN, "vadd-contract-selftest-asan"), vadd_selftest,
+             ["g++", "-O1", "-std=c++17", *san, vadd_selftest[0], "-o", "{out}"]),
+            (n(BIN, "io-trace-selftest-asan"), trace_selftest,
+             ["g++", "-O1", "-std=c++17", *san, trace_selftest[0], "-pthread", "-ldl", "-o", "{out}"]),
+            (n(BIN, "io-trace-selftest-tsan"), trace_selftest,
+             ["g++", "-O1", "-std=c++17", "-fsanitize=thread", "-fno-omit-frame-pointer", "-g", trace_selftest[0],
+              "-pthread", "-ldl", "-o", "{out}"]),
             (n(BIN, "sampler-selftest-tsan"), [n("native/sampler_selftest.cpp"), n("native/sampler_core.h")],
              ["g++", "-O1", "-std=c++17", "-fsanitize=thread", "-fno-omit-frame-pointer", "-g",
               n("native/sampler_selftest.cpp"), "-pthread", "-o", "{out}"]),
@@ -120,7 +137,7 @@ def targets(sanitize=False, cpu_only=False):
             raise SystemExit("hipcc not found: cannot build gfx950 targets")
         ho = [hip, f"--offload-arch={ARCH}", "-O3", "-std=c++17"]
         # each header with what it includes: a program depends on what it launches
-        base = [n("kernels/gpu_common.h"), n("kernels/gpu_host.h"), n("kernels/check_core.h")]
+        base = [n("kernels/gpu_common.h"), n("kernels/gpu_host.h"), n("kernels/check_core.h"), n("kernels/vadd_contract.h")]
         chk = [n("kernels/mfma_check.h"), *base]
         lp = [n("kernels/mfma_check_lp.h"), *chk]
         cu = [n("kernels/cu_check.h"), *base]
@@ -130,6 +147,7 @@ def targets(sanitize=False, cpu_only=False):
             (n(BIN, "rocm-vector-add"), [n("kernels/vector_add.hip"), *base], [*ho, n("kernels/vector_add.hip"), "-o", "{out}"]),
             # the HIP-free pod workload: a bare gfx950 code object, then the HSA host embedding it
             (n(BIN, "hsa-vector-add"), [n("kernels/hsa_vector_add.cpp"), n("kernels/vadd_kernel.hip"),
+                                        n("kernels/vadd_contract.h"), n("kernels/hsa_min.h"), n("native/io_trace.h"),
                                         n("native/sysfs_prefetch.h")],
              ["sh", "-c", f'"$0" --offload-arch={ARCH} -O3 --offload-device-only --no-gpu-bundle-output -c '
               f'{n("kernels/vadd_kernel.hip")} -o {n(OUT, "lib", "vadd_" + ARCH + ".co")} && '

@@ -52,6 +52,16 @@ def test_both_modes_agree(n, hip_identity):
     assert p_on is True and p_off is False
 
 
+@pytest.mark.parametrize("n", [1, 1025])   # the smallest size, and the smallest at which the two programs' grids differ
+def test_hip_and_hsa_builds_print_the_same_lines(n):
+    hip = vadd("-n", str(n), binary="rocm-vector-add")
+    hsa = vadd("-n", str(n))
+    for r in (hip, hsa):
+        assert r.returncode == 0 and r.stdout.endswith("Test PASSED\n"), r.stdout + r.stderr
+    assert hip.stdout.splitlines() == hsa.stdout.splitlines()
+    assert len(hsa.stdout.splitlines()) == 3 and f"[Vector addition of {n} elements]" in hsa.stdout
+
+
 def prefetch_trace(stderr):
     m = re.search(r"^\[trace\] prefetch (\S+) (.*)$", stderr, re.M)
     assert m, stderr
