@@ -48,14 +48,15 @@ def _np(x, dtype):
     return np.ascontiguousarray(x, dtype=dtype)
 
 
-def vector_add_tensors(a, b, device: int = 0):
-    """c = a + b with the pod workload's gfx950 vadd kernel; torch in → torch out."""
+def vector_add_tensors(a, b, device: int = 0, grid: int = 0):
+    """c = a + b with the pod workload's gfx950 vadd kernel; torch in → torch out. `grid` is the number
+    of workgroups, 0 for the production grid."""
     import numpy as np
     import torch
     av, bv = _np(a, np.float32).ravel(), _np(b, np.float32).ravel()
     if av.shape != bv.shape:
         raise ValueError(f"shape mismatch {av.shape} vs {bv.shape}")
-    return torch.from_numpy(np.asarray(_need().vector_add_arrays(av, bv, device))).reshape(tuple(a.shape))
+    return torch.from_numpy(np.asarray(_need().vector_add_arrays(av, bv, device, grid))).reshape(tuple(a.shape))
 
 
 def mfma_tile(a, b, device: int = 0):
@@ -219,18 +220,47 @@ def cu_check_dump(block: int, seed: int = 0x5EED, device: int = 0) -> dict:
     return d
 
 
-def hbm_pattern(n16: int, seed: int = 0x5EED, device: int = 0):
+# `grid` below is the number of workgroups to launch: 0 takes the production grid (sized from the CU
+# count), anything else up to 65536 lets a test reach empty, ragged and unrolled-loop chunks at a few KiB.
+def hbm_pattern(n16: int, seed: int = 0x5EED, device: int = 0, grid: int = 0):
     """The HBM probe's write pattern for n16 16-byte words, as uint32 words."""
     import numpy as np
-    return np.asarray(_need().hbm_pattern(n16, seed, device))
+    return np.asarray(_need().hbm_pattern(n16, seed, device, grid))
 
 
-def hbm_verify(words, seed: int = 0x5EED, device: int = 0) -> int:
+def hbm_verify(words, seed: int = 0x5EED, device: int = 0, grid: int = 0) -> int:
     """Mismatching 32-bit words of `words` against the probe pattern (the probe's verify kernel)."""
     import numpy as np
-    return int(_need().hbm_verify_words(_np(words, np.uint32).ravel(), seed, device))
+    return int(_need().hbm_verify_words(_np(words, np.uint32).ravel(), seed, device, grid))
 
 
-def hbm_copy(words, device: int = 0):
+def hbm_read(words, grid: int = 0, device: int = 0) -> int:
+    """The probe's read kernel over `words`: it XORs every 32-bit word it loads, per lane, and a lane
+    whose XOR is 0x9e3779b9 stores that value; returns what was stored, else 0."""
     import numpy as np
-    return np.asarray(_need().hbm_copy_words(_np(words, np.uint32).ravel(), device))
+    return int(_need().hbm_read_words(_np(words, np.uint32).ravel(), grid, device))
+
+
+def hbm_copy(words, device: int = 0, grid: int = 0):
+    """`words` through the probe's copy kernel, into a destination that held 0xff bytes."""
+    import numpy as np
+    return np.asarray(_need().hbm_copy_words(_np(words, np.uint32).ravel(), device, grid))
+
+
+# ---- hsa-vector-add's kernels (kernels/vadd_kernel.hip) from the code object that program embeds
+VADD_CODE_OBJECT = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "_native", "lib", "vadd_gfx950.co")
+
+
+def hsa_vadd_arrays(a, b, groups: int, device: int = 0):
+    """c = a + b with `amdkube_vadd` on `groups` workgroups; float32 numpy in and out."""
+    import numpy as np
+    av, bv = _np(a, np.float32).ravel(), _np(b, np.float32).ravel()
+    if av.shape != bv.shape:
+        raise ValueError(f"shape mismatch {av.shape} vs {bv.shape}")
+    return np.asarray(_need().hsa_vadd_arrays(VADD_CODE_OBJECT, av, bv, groups, device))
+
+
+def hsa_copy_array(src, groups: int, device: int = 0):
+    """`src` through `amdkube_copy` on `groups` workgroups; float32 numpy in and out, bit for bit."""
+    import numpy as np
+    return np.asarray(_need().hsa_copy_array(VADD_CODE_OBJECT, _np(src, np.float32).ravel(), groups, device))

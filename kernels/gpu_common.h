@@ -249,6 +249,7 @@ inline VaddResult run_vector_add(size_t n, int dev) {
   std::vector<float> ha(n), hb(n);
   vadd_fill_inputs(ha.data(), hb.data(), n);
   DevBuf da(ha), db(hb), dc(n * sizeof(float));
+  dc.fill(0xff);   // NaN, as hsa-vector-add fills its c: an element the kernel never wrote is a mismatch
   GpuTimer timer;
   const int grid = stream_grid((n + 3) / 4, info.cu_count, VADD_BLOCKS_PER_CU);
   r.kernel_ms = timer.time([&] {
@@ -261,51 +262,150 @@ inline VaddResult run_vector_add(size_t n, int dev) {
   return r;
 }
 
-// ---- host-supplied data: the kernels on caller-provided inputs (numerics vs torch fp32)
+// ---- host-supplied data: the kernels on caller-provided inputs (bitwise against numpy / torch on the CPU)
+// `grid` is the number of workgroups to launch; 0 takes the production grid, which comes from the CU count
+// and reaches its cap only at tens of MiB. A test passes its own to get, at a few KiB, chunks that are
+// empty, ragged, or long enough for the unrolled loops (tests/test_gpu_stream_kernels.py). Every kernel
+// here is right at any grid: it derives its chunks or its stride from gridDim.
+constexpr int HOST_GRID_MAX = 65536;
+
+inline int host_grid(int grid, int production) {
+  if (grid < 0 || grid > HOST_GRID_MAX) throw std::invalid_argument("grid must be in [0, 65536] (0: the production grid)");
+  return grid ? grid : production;
+}
+
+// Outputs start as 0xff bytes (NaN as fp32), so an element the kernel skipped cannot pass on what the
+// allocation happened to hold.
 // c = a + b on the device with the pod workload's vadd_kernel
-inline std::vector<float> vector_add_host(const std::vector<float>& a, const std::vector<float>& b, int dev) {
+inline std::vector<float> vector_add_host(const std::vector<float>& a, const std::vector<float>& b, int dev, int grid = 0) {
   if (a.size() != b.size()) throw std::invalid_argument("a and b differ in length");
   AK_HIP(hipSetDevice(dev));
   const size_t n = a.size();
+  grid = host_grid(grid, stream_grid((n + 3) / 4, dev_info(dev).cu_count, VADD_BLOCKS_PER_CU));
   DevBuf da(a), db(b), dc(n * sizeof(float));
-  const int grid = stream_grid((n + 3) / 4, dev_info(dev).cu_count, VADD_BLOCKS_PER_CU);
+  dc.fill(0xff);
   hipLaunchKernelGGL(vadd_kernel, dim3(grid), dim3(VADD_WG), 0, 0, da.as<const float>(), db.as<const float>(), dc.as<float>(), n);
   AK_HIP(hipGetLastError());
   return dc.download<float>();
 }
 
-// the HBM probe's write pattern for n16 16-byte words (checked against a torch re-derivation)
-inline std::vector<uint32_t> hbm_pattern_host(size_t n16, uint32_t seed, int dev) {
+// the HBM probe's write pattern for n16 16-byte words (checked against a numpy re-derivation)
+inline std::vector<uint32_t> hbm_pattern_host(size_t n16, uint32_t seed, int dev, int grid = 0) {
   AK_HIP(hipSetDevice(dev));
+  grid = host_grid(grid, write_front_grid(dev_info(dev).cu_count));
   DevBuf d(n16 * 16);
-  const int grid = write_front_grid(dev_info(dev).cu_count);
+  d.fill(0xff);
   hipLaunchKernelGGL(hbm_write_kernel, dim3(grid), dim3(256), 0, 0, d.as<v4u>(), n16, seed);
   AK_HIP(hipGetLastError());
   return d.download<uint32_t>();
 }
 
 // the probe's verify kernel on caller data: mismatching 32-bit words against the pattern
-inline unsigned long long hbm_verify_host(const std::vector<uint32_t>& words, uint32_t seed, int dev) {
+inline unsigned long long hbm_verify_host(const std::vector<uint32_t>& words, uint32_t seed, int dev, int grid = 0) {
   if (words.size() % 4) throw std::invalid_argument("need a whole number of 16-byte words");
   AK_HIP(hipSetDevice(dev));
   const size_t n16 = words.size() / 4;
+  grid = host_grid(grid, stream_grid(n16, dev_info(dev).cu_count, HBM_BLOCKS_PER_CU));
   DevBuf d(words), e(sizeof(unsigned long long), DevBuf::zeroed);
-  const int grid = stream_grid(n16, dev_info(dev).cu_count, HBM_BLOCKS_PER_CU);
   hipLaunchKernelGGL(hbm_verify_kernel, dim3(grid), dim3(256), 0, 0, d.as<const v4u>(), n16, seed, e.as<unsigned long long>());
   AK_HIP(hipGetLastError());
   return e.download<unsigned long long>()[0];
 }
 
-// the probe's copy kernel on caller data
-inline std::vector<uint32_t> hbm_copy_host(const std::vector<uint32_t>& words, int dev) {
+// the probe's read kernel on caller data: the XOR of every 32-bit word it loaded, if that is the one value
+// the kernel stores (0x9e3779b9), else 0. A buffer of zeros with that word in one place says whether the
+// place was read.
+inline uint32_t hbm_read_host(const std::vector<uint32_t>& words, int grid, int dev) {
   if (words.size() % 4) throw std::invalid_argument("need a whole number of 16-byte words");
   AK_HIP(hipSetDevice(dev));
   const size_t n16 = words.size() / 4;
+  grid = host_grid(grid, stream_grid(n16, dev_info(dev).cu_count, HBM_BLOCKS_PER_CU));
+  DevBuf d(words), sink(sizeof(uint32_t), DevBuf::zeroed);
+  hipLaunchKernelGGL(hbm_read_kernel, dim3(grid), dim3(256), 0, 0, d.as<const v4u>(), n16, sink.as<uint32_t>());
+  AK_HIP(hipGetLastError());
+  return sink.download<uint32_t>()[0];
+}
+
+// the probe's copy kernel on caller data
+inline std::vector<uint32_t> hbm_copy_host(const std::vector<uint32_t>& words, int dev, int grid = 0) {
+  if (words.size() % 4) throw std::invalid_argument("need a whole number of 16-byte words");
+  AK_HIP(hipSetDevice(dev));
+  const size_t n16 = words.size() / 4;
+  grid = host_grid(grid, stream_grid(n16, dev_info(dev).cu_count, HBM_COPY_BLOCKS_PER_CU));
   DevBuf s(words), d(n16 * 16);
-  const int grid = stream_grid(n16, dev_info(dev).cu_count, HBM_COPY_BLOCKS_PER_CU);
+  d.fill(0xff);
   hipLaunchKernelGGL(hbm_copy_kernel, dim3(grid), dim3(256), 0, 0, s.as<const v4u>(), d.as<v4u>(), n16);
   AK_HIP(hipGetLastError());
   return d.download<uint32_t>();
+}
+
+// ---- hsa-vector-add's kernels in this process: the bare code object that program embeds (vadd_kernel.hip,
+// built by native/build.py), loaded from its file and launched through HIP's module API with the packed
+// kernarg blocks of hsa_vector_add.cpp. `groups` is both the grid and the kernels' last argument.
+struct GpuModule {
+  hipModule_t m = nullptr;
+  explicit GpuModule(const std::string& path) {
+    hipError_t e = hipModuleLoad(&m, path.c_str());
+    if (e != hipSuccess) throw std::runtime_error("hipModuleLoad(" + path + "): " + hipGetErrorString(e));
+  }
+  ~GpuModule() { (void)hipModuleUnload(m); }
+  GpuModule(const GpuModule&) = delete;
+  GpuModule& operator=(const GpuModule&) = delete;
+  hipFunction_t function(const char* name) const {
+    hipFunction_t f = nullptr;
+    AK_HIP(hipModuleGetFunction(&f, m, name));
+    return f;
+  }
+  // one launch of groups x VADD_WG on the null stream with `size` bytes of kernel arguments
+  void launch(hipFunction_t f, unsigned groups, void* args, size_t size) const {
+    void* config[] = {HIP_LAUNCH_PARAM_BUFFER_POINTER, args, HIP_LAUNCH_PARAM_BUFFER_SIZE, &size, HIP_LAUNCH_PARAM_END};
+    AK_HIP(hipModuleLaunchKernel(f, groups, 1, 1, VADD_WG, 1, 1, 0, nullptr, nullptr, config));
+  }
+};
+
+struct __attribute__((packed)) CoVaddArgs {   // amdkube_vadd's kernarg segment: hsa_vector_add.cpp, Args
+  const float *a, *b;
+  float* c;
+  unsigned long long n;
+  unsigned groups;
+};
+struct __attribute__((packed)) CoCopyArgs {   // amdkube_copy's: hsa_vector_add.cpp, CopyArgs
+  const float* src;
+  float* dst;
+  unsigned long long n;
+  unsigned groups;
+};
+static_assert(sizeof(CoVaddArgs) == 36 && sizeof(CoCopyArgs) == 28, "the kernarg segment sizes hsa-vector-add checks");
+
+inline unsigned co_groups(int groups) {
+  if (groups < 1 || groups > HOST_GRID_MAX) throw std::invalid_argument("groups must be in [1, 65536]");
+  return static_cast<unsigned>(groups);
+}
+
+// c = a + b with amdkube_vadd of the code object at `path`
+inline std::vector<float> co_vadd_host(const std::string& path, const std::vector<float>& a, const std::vector<float>& b,
+                                       int groups, int dev) {
+  if (a.size() != b.size()) throw std::invalid_argument("a and b differ in length");
+  const unsigned g = co_groups(groups);
+  AK_HIP(hipSetDevice(dev));
+  DevBuf da(a), db(b), dc(a.size() * sizeof(float));
+  dc.fill(0xff);
+  GpuModule mod(path);   // unloaded on every way out, before the buffers go; the download waits for the kernel
+  CoVaddArgs args{da.as<const float>(), db.as<const float>(), dc.as<float>(), a.size(), g};
+  mod.launch(mod.function("amdkube_vadd"), g, &args, sizeof args);
+  return dc.download<float>();
+}
+
+// a copy of src made by amdkube_copy of the code object at `path`
+inline std::vector<float> co_copy_host(const std::string& path, const std::vector<float>& src, int groups, int dev) {
+  const unsigned g = co_groups(groups);
+  AK_HIP(hipSetDevice(dev));
+  DevBuf ds(src), dd(src.size() * sizeof(float));
+  dd.fill(0xff);
+  GpuModule mod(path);
+  CoCopyArgs args{ds.as<const float>(), dd.as<float>(), src.size(), g};
+  mod.launch(mod.function("amdkube_copy"), g, &args, sizeof args);
+  return dd.download<float>();
 }
 
 // C[32x32] fp32 = A[32xK] bf16 * B[Kx32] bf16 on one wave (K a multiple of 16, <= 1024)

@@ -77,7 +77,11 @@ struct DevBuf {
   DevBuf& operator=(const DevBuf&) = delete;
   template <class T>
   T* as() const { return static_cast<T*>(p); }
-  void zero() { AK_HIP(hipMemset(p, 0, bytes)); }
+  void zero() { fill(0); }
+  // every byte; 0xff makes each float a NaN and each word all ones: a tripwire for an element nobody wrote
+  void fill(int byte) {
+    if (bytes) AK_HIP(hipMemset(p, byte, bytes));
+  }
   // the first n elements (all of them by default), after everything queued on the device
   template <class T>
   std::vector<T> download(size_t n = ~size_t(0)) const {

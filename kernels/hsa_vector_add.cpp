@@ -143,7 +143,7 @@ void allocate_and_fill(Pod& p, const Pools& pools, size_t n) {
   p.dc = p.db + p.stride;
   check(hsa_amd_agents_allow_access(1, &p.gpu, nullptr, p.ha), "host access");
   vadd_fill_inputs(p.ha, p.hb, n);
-  std::memset(p.hc, 0xff, n * sizeof(float));
+  std::memset(p.hc, 0xff, n * sizeof(float));   // NaN: an element no kernel wrote counts as a mismatch
 }
 
 // the completion signal, the three packets' arguments and the queue

@@ -165,34 +165,59 @@ PYBIND11_MODULE(_hipops, m) {
   // caller-supplied data (numpy arrays, e.g. torch.Tensor.numpy()) → the same kernels
   m.def(
       "vector_add_arrays",
-      [](array_in<float> a, array_in<float> b, int dev) {
+      [](array_in<float> a, array_in<float> b, int dev, int grid) {
         const std::vector<float> va = to_vec(a), vb = to_vec(b);
-        const std::vector<float> vc = nogil([&] { return amdkube::vector_add_host(va, vb, dev); });
+        const std::vector<float> vc = nogil([&] { return amdkube::vector_add_host(va, vb, dev, grid); });
         return py::array_t<float>(vc.size(), vc.data());
       },
-      py::arg("a"), py::arg("b"), py::arg("device") = 0);
+      py::arg("a"), py::arg("b"), py::arg("device") = 0, py::arg("grid") = 0);
+  // grid: workgroups to launch, 0 for the production grid (kernels/gpu_common.h, host_grid)
   m.def(
       "hbm_pattern",
-      [](size_t n16, uint32_t seed, int dev) {
-        const std::vector<uint32_t> w = nogil([&] { return amdkube::hbm_pattern_host(n16, seed, dev); });
+      [](size_t n16, uint32_t seed, int dev, int grid) {
+        const std::vector<uint32_t> w = nogil([&] { return amdkube::hbm_pattern_host(n16, seed, dev, grid); });
         return py::array_t<uint32_t>(w.size(), w.data());
       },
-      py::arg("n16"), py::arg("seed") = 0x5eedu, py::arg("device") = 0);
+      py::arg("n16"), py::arg("seed") = 0x5eedu, py::arg("device") = 0, py::arg("grid") = 0);
   m.def(
       "hbm_verify_words",
-      [](array_in<uint32_t> words, uint32_t seed, int dev) {
+      [](array_in<uint32_t> words, uint32_t seed, int dev, int grid) {
         const std::vector<uint32_t> w = to_vec(words);
-        return nogil([&] { return amdkube::hbm_verify_host(w, seed, dev); });
+        return nogil([&] { return amdkube::hbm_verify_host(w, seed, dev, grid); });
       },
-      py::arg("words"), py::arg("seed") = 0x5eedu, py::arg("device") = 0);
+      py::arg("words"), py::arg("seed") = 0x5eedu, py::arg("device") = 0, py::arg("grid") = 0);
+  m.def(
+      "hbm_read_words",
+      [](array_in<uint32_t> words, int grid, int dev) {
+        const std::vector<uint32_t> w = to_vec(words);
+        return nogil([&] { return amdkube::hbm_read_host(w, grid, dev); });
+      },
+      py::arg("words"), py::arg("grid") = 0, py::arg("device") = 0);
   m.def(
       "hbm_copy_words",
-      [](array_in<uint32_t> words, int dev) {
+      [](array_in<uint32_t> words, int dev, int grid) {
         const std::vector<uint32_t> w = to_vec(words);
-        const std::vector<uint32_t> o = nogil([&] { return amdkube::hbm_copy_host(w, dev); });
+        const std::vector<uint32_t> o = nogil([&] { return amdkube::hbm_copy_host(w, dev, grid); });
         return py::array_t<uint32_t>(o.size(), o.data());
       },
-      py::arg("words"), py::arg("device") = 0);
+      py::arg("words"), py::arg("device") = 0, py::arg("grid") = 0);
+  // hsa-vector-add's kernels, from the code object it embeds (co_path: amdkube/_native/lib/vadd_gfx950.co)
+  m.def(
+      "hsa_vadd_arrays",
+      [](const std::string& co_path, array_in<float> a, array_in<float> b, int groups, int dev) {
+        const std::vector<float> va = to_vec(a), vb = to_vec(b);
+        const std::vector<float> vc = nogil([&] { return amdkube::co_vadd_host(co_path, va, vb, groups, dev); });
+        return py::array_t<float>(vc.size(), vc.data());
+      },
+      py::arg("co_path"), py::arg("a"), py::arg("b"), py::arg("groups"), py::arg("device") = 0);
+  m.def(
+      "hsa_copy_array",
+      [](const std::string& co_path, array_in<float> src, int groups, int dev) {
+        const std::vector<float> vs = to_vec(src);
+        const std::vector<float> vo = nogil([&] { return amdkube::co_copy_host(co_path, vs, groups, dev); });
+        return py::array_t<float>(vo.size(), vo.data());
+      },
+      py::arg("co_path"), py::arg("src"), py::arg("groups"), py::arg("device") = 0);
   m.def(
       "mfma_tile",
       [](array_in<uint16_t> a_bits, array_in<uint16_t> b_bits, int k, int dev) {

@@ -1,7 +1,7 @@
 // Self-test of kernels/vadd_contract.h on the CPU (no HIP, no HSA): the parser, the inputs, the
 // verification and the grid against transcriptions of the two copies the header replaced
 // (rocm-vector-add's and hsa-vector-add's), and every printer against the literal lines those programs
-// printed. Built plain and with ASan/UBSan (native/build.py), run by tests/test_vadd_contract.py.
+// printed. The verification differs from the two copies in one way, on purpose: a NaN difference counts. Built plain and with ASan/UBSan (native/build.py), run by tests/test_vadd_contract.py.
 // Prints "OK ..." and exits 0, or says what failed.
 #include <cmath>
 #include <cstdint>
@@ -140,16 +140,39 @@ static void test_verification() {
   count3({}, {}, {}, 0);
 }
 
-// Present behaviour, recorded so that the fix flips these expectations: NaN compares false both ways, so
-// a NaN in c (hsa-vector-add pre-fills c with 0xff bytes, which is NaN) or in a sum passes.
-static void test_nan_passes_present_behaviour() {
+// The one intended difference from the two loops: a difference that is NaN counts, 1 per element. Those
+// loops compared "> 1e-5", which is false for NaN, so they return 0 on every input here.
+static void count_nan(const std::vector<float>& a, const std::vector<float>& b, const std::vector<float>& c, size_t expect) {
+  CHECK(vadd_count_mismatches(a.data(), b.data(), c.data(), a.size()) == expect);
+  CHECK(old_hip_count(a.data(), b.data(), c.data(), a.size()) == 0);
+  CHECK(old_hsa_count(a.data(), b.data(), c.data(), a.size()) == 0);
+}
+
+static void test_nan_counts() {
   const float nan = std::numeric_limits<float>::quiet_NaN(), inf = std::numeric_limits<float>::infinity();
   float ff;
   std::memset(&ff, 0xff, sizeof ff);
   CHECK(ff != ff);
-  count3({0.5f, 0.5f}, {0.25f, 0.25f}, {nan, ff}, 0);
-  count3({nan}, {0.25f}, {0.75f}, 0);
-  count3({inf}, {0.25f}, {inf}, 0);    // inf - inf is NaN too
+  count_nan({0.5f}, {0.25f}, {nan}, 1);                   // NaN in c
+  count_nan({0.5f}, {0.25f}, {-nan}, 1);
+  count_nan({0.5f}, {0.25f}, {ff}, 1);                    // the 0xff fill: an element the GPU never wrote
+  count_nan({nan}, {0.25f}, {0.75f}, 1);                  // a NaN input
+  count_nan({0.25f}, {nan}, {nan}, 1);                    // ... even where c is the NaN the GPU would give
+  count_nan({inf}, {0.25f}, {inf}, 1);                    // inf - inf is NaN too
+  count_nan({-inf}, {0.25f}, {-inf}, 1);
+  // among good elements each is counted once, wherever it stands: a whole run whose c stayed at the fill
+  const size_t n = 1025;
+  std::vector<float> a(n), b(n), c(n);
+  vadd_fill_inputs(a.data(), b.data(), n);
+  for (size_t i = 0; i < n; ++i) c[i] = a[i] + b[i];
+  std::vector<float> x = c;
+  x[0] = ff, x[512] = nan, x[n - 1] = ff;
+  count_nan(a, b, x, 3);
+  x[7] += 2e-5f;                                          // next to an ordinary mismatch, which all three see
+  CHECK(vadd_count_mismatches(a.data(), b.data(), x.data(), n) == 4);
+  CHECK(old_hip_count(a.data(), b.data(), x.data(), n) == 1 && old_hsa_count(a.data(), b.data(), x.data(), n) == 1);
+  std::memset(c.data(), 0xff, n * sizeof(float));
+  count_nan(a, b, c, n);
 }
 
 // ---- the grid: the two formulas it replaced
@@ -235,13 +258,13 @@ int main() {
   test_parser();
   test_inputs();
   test_verification();
-  test_nan_passes_present_behaviour();
+  test_nan_counts();
   test_grid();
   test_printers();
   if (failures) {
     std::fprintf(stderr, "%d check(s) failed\n", failures);
     return 1;
   }
-  std::printf("OK vadd_contract: parser, inputs, verification, grid, printers\n");
+  std::printf("OK vadd_contract: parser, inputs, verification, nan counts, grid, printers\n");
   return 0;
 }

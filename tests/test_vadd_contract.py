@@ -1,6 +1,7 @@
 """kernels/vadd_contract.h on CPU: the flags, inputs, verification, grid and output lines that
 rocm-vector-add and hsa-vector-add share, through the stand-alone self-test built plain and with
-ASan/UBSan. See native/vadd_contract_selftest.cpp for what it checks."""
+ASan/UBSan. See native/vadd_contract_selftest.cpp for what it checks; among it, that the verification
+counts a NaN (in c, from the 0xff fill, from a NaN input, from inf - inf) where the two loops it replaced did not."""
 import os
 import subprocess
 import sys
@@ -22,4 +23,5 @@ def built():
 def test_vadd_contract_selftest(binary):
     r = subprocess.run([os.path.join(BIN, binary)], capture_output=True, text=True, timeout=120)
     assert r.returncode == 0 and r.stdout.startswith("OK"), r.stdout + r.stderr[-3000:]
+    assert "nan counts" in r.stdout, r.stdout     # a NaN difference is a mismatch: the cases ran
     assert "Sanitizer" not in r.stderr and "runtime error" not in r.stderr, r.stderr[-3000:]
