@@ -897,6 +897,17 @@ def device_plugin_parser():
                     help="on-device checks before a GPU is advertised: none, or a comma list over hbm (HBM pattern "
                          "probe), mfma (bf16 matrix-core check), mfma-lp (FP8 / MXFP8 / MXFP4 matrix-core check) and cu "
                          "(per-CU check: LDS march, vector ALU pipes, transcendental unit, with the CU of each error)")
+    def mib(text):
+        try:
+            n = int(text)
+        except ValueError:
+            raise argparse.ArgumentTypeError(f"not a number of MiB: {text!r}")
+        if n < 0:
+            raise argparse.ArgumentTypeError("must not be negative (0: off)")
+        return n
+    ap.add_argument("--hbm-check-mib", default=0, type=mib, metavar="N",
+                    help="also march N MiB of every GPU's HBM (hbm-check --mib N: every bit read in both states, errors "
+                         "with their offset and 2 MiB page) after the --health-probe list, or alone with none; 0: off")
     ap.add_argument("--max-gpus", type=int, default=None, help="advertise only the first N physical GPUs")
     ap.add_argument("--resource-naming", default="single", choices=("single", "mixed"),
                     help="partitioned GPUs: single=amd.com/gpu for all, mixed=amd.com/<cpx>_<nps> per partition type")
@@ -929,7 +940,7 @@ def device_plugin(argv):
         backend = open_backend(a.backend, a.fixture, a.max_gpus, a.partition)
         plugins = make_plugins(backend, a.resource_naming, a.resource_name, plugins_dir=a.plugins_dir,
                                health_interval=a.health_interval, health_probe=a.health_probe,
-                               health_state=state or None)
+                               health_state=state or None, hbm_check_mib=a.hbm_check_mib)
         for p in plugins:
             await p.start()
             if a.register_v1beta1:

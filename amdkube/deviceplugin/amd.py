@@ -158,6 +158,20 @@ def all_health_probes() -> dict:
     return {**HEALTH_PROBES, **HEALTH_PROBES_CU}
 
 
+# The HBM march is no entry of those tables: it needs a size. `--hbm-check-mib N` runs `hbm-check --mib N`
+# on every GPU after the probe list (also when the list is `none`). Its time limit comes from its wall
+# time on an MI355X (docs/PERFORMANCE.md, "HBM check"): 0.24-0.37 s from process start to exit at 2 and at
+# 8 GiB alike, of which the march is 1.1 ms per GiB. Both terms get about a hundred times that, so a
+# cold runtime on a busy node passes and a hung check still ends: 30 s, and 0.1 s per GiB.
+HBM_CHECK_BASE_S = 30.0
+HBM_CHECK_S_PER_GIB = 0.1
+
+
+def hbm_check_timeout(mib: int) -> float:
+    """Seconds `hbm-check --mib mib` gets before the plugin gives up on it."""
+    return HBM_CHECK_BASE_S + HBM_CHECK_S_PER_GIB * mib / 1024.0
+
+
 def parse_health_probe(spec: str) -> list[str]:
     """`none`, or a comma list over all_health_probes() → the probes to run, HBM first."""
     known = all_health_probes()
@@ -175,8 +189,11 @@ class AMDGPUPlugin(DevicePluginServer):
     def __init__(self, backend: Backend, resource_name: str = RESOURCE, plugins_dir: str = DEVICE_PLUGINS_PATH,
                  health_interval: float = 10.0, health_probe: str = "none", dev_root: str = "/dev",
                  ecc_threshold: int = 0, expose_card: bool = True, init_timeout: int = 10,
-                 devices: list[dict] | None = None, health_state: str | None = None):
+                 devices: list[dict] | None = None, health_state: str | None = None, hbm_check_mib: int = 0):
         super().__init__(resource_name, plugins_dir, init_timeout)
+        if hbm_check_mib < 0:
+            raise ValueError("hbm_check_mib must not be negative (0: no HBM march)")
+        self.hbm_check_mib = int(hbm_check_mib)
         self.backend = backend
         self.health_interval = health_interval
         self.health_probe = health_probe
@@ -211,7 +228,7 @@ class AMDGPUPlugin(DevicePluginServer):
     async def start(self):
         for g in self.gpus:             # the RAS baseline new faults are judged against
             self.monitor.snapshot(g["index"])
-        if self.probes:
+        if self.probes or self.hbm_check_mib:
             await self._probe_all()
         self._check_health(push=False)
         await super().start()
@@ -283,18 +300,21 @@ class AMDGPUPlugin(DevicePluginServer):
                 log.error("health check failed: %s", e)
 
     async def _probe_all(self):
-        """Run the configured on-device probes (HBM pattern, matrix-core checks, per-CU check) on each GPU
-        (subprocess → isolated HIP context); the first failure takes the GPU out of service."""
+        """Run the configured on-device probes (HBM pattern, matrix-core checks, per-CU check, then the HBM
+        march if hbm_check_mib is set) on each GPU (subprocess → isolated HIP context); the first failure
+        takes the GPU out of service and ends its chain."""
         known = all_health_probes()
+        runs = [(*known[probe], 60) for probe in self.probes]
+        if self.hbm_check_mib:
+            runs.append(("hbm-check", ["--mib", str(self.hbm_check_mib)], hbm_check_timeout(self.hbm_check_mib)))
         for g in self.gpus:
             did = device_id(g)
             env = {k: v for k, v in os.environ.items() if k not in ("HIP_VISIBLE_DEVICES", "CUDA_VISIBLE_DEVICES")}
             env["ROCR_VISIBLE_DEVICES"] = visibility_token(g)
-            for probe in self.probes:
-                name, args = known[probe]
+            for name, args, limit in runs:
                 try:
                     r = await asyncio.to_thread(subprocess.run, [os.path.join(BIN_DIR, name), *args], env=env,
-                                                capture_output=True, text=True, timeout=60)
+                                                capture_output=True, text=True, timeout=limit)
                     if r.returncode != 0:
                         self.reasons[did] = f"probe: {name} failed rc={r.returncode} {r.stdout.strip()[-200:]}"
                 except Exception as e:

@@ -220,6 +220,55 @@ def cu_check_dump(block: int, seed: int = 0x5EED, device: int = 0) -> dict:
     return d
 
 
+def hbm_check(mib: int | None = None, rounds: int = 1, seed: int = 0x5EED, selftest_flips: int = 0, chunk_mib: int = 1024,
+              hold_ms: int = 0, device: int = 0, free_fraction: float | None = None) -> dict:
+    """The HBM integrity check (hbm-check in process, kernels/hbm_check.h): a march over `mib` MiB
+    (default 1024), or over the share `free_fraction`, in (0, 0.95], of the device's free memory, in chunks
+    of `chunk_mib` MiB. Each of `rounds` rounds writes an address-hashed background, reads it and writes
+    its complement going up, reads that and writes the background going down, and reads it once more,
+    every step over the whole region, with a host sleep of `hold_ms` between the second and the third.
+    `selftest_flips` (at most 64) corrupts that many slots of the first chunk between those two steps of
+    round 0, which the check must then report. The result carries `bytes`, `chunks` (bytes of each),
+    `ms`, `alloc_ms`, `march_gbps`, `errors`, `bit_errors`, `transient`, `persistent`, `records_dropped`,
+    `bad_pages` (`offset` in the region, `chunk`, `errors`; at most 32, with `bad_pages_total`) and
+    `first_errors`: `round`, `pass`, `chunk`, `slot`, `word`, `got`, `want`, `again` and the `xcc`, `se`,
+    `sh`, `cu` of the wave that read it."""
+    from . import hbmcheck
+    if mib is not None and free_fraction is not None:
+        raise ValueError("give the region as mib or as free_fraction, not both")
+    if mib is None and free_fraction is None:
+        mib = 1024
+    if mib is not None and int(mib) < 2:
+        raise ValueError("mib must be at least 2 (one 2 MiB page)")
+    if free_fraction is not None and not 0 < float(free_fraction) <= hbmcheck.FREE_FRACTION_MAX:
+        raise ValueError("free_fraction must be in (0, 0.95]")
+    if rounds < 1:
+        raise ValueError("rounds must be at least 1")
+    if not 0 <= int(selftest_flips) <= hbmcheck.RECORDS:
+        raise ValueError(f"selftest_flips must be in [0, {hbmcheck.RECORDS}]")
+    r = dict(_need().hbm_check(int(mib or 0), float(free_fraction or 0.0), int(chunk_mib), int(rounds), seed,
+                               int(selftest_flips), int(hold_ms), device))
+    r["chunks"] = [int(c) for c in r["chunks"]]
+    for k in ("first_errors", "bad_pages"):
+        r[k] = [dict(e) for e in r[k]]
+    return r
+
+
+def hbm_march_pass(words, seed: int, invert: bool, down: bool, write: bool, device: int = 0, grid: int = 0) -> dict:
+    """One launch of the check's march kernel on `words` (uint32, four to a 16-byte slot): compare every
+    word with the pattern of `seed`, complemented if `invert`, walking every workgroup's share downwards
+    if `down`, and if `write` store the complement of what was expected. `grid` is the number of workgroups,
+    0 for the production grid, as in the hbm_* wrappers below. Returns `words` after the pass,
+    `errors`, `bit_errors`, `transient`, `persistent`, `records_dropped`, `page_errors` (one count per
+    2 MiB) and `records` (at most 64, as `first_errors` of hbm_check)."""
+    import numpy as np
+    r = dict(_need().hbm_march_pass(_np(words, np.uint32).ravel(), seed, 0xFFFFFFFF if invert else 0, bool(down),
+                                    bool(write), device, grid))
+    r["words"], r["page_errors"] = np.asarray(r["words"]), np.asarray(r["page_errors"])
+    r["records"] = [dict(e) for e in r["records"]]
+    return r
+
+
 # `grid` below is the number of workgroups to launch: 0 takes the production grid (sized from the CU
 # count), anything else up to 65536 lets a test reach empty, ragged and unrolled-loop chunks at a few KiB.
 def hbm_pattern(n16: int, seed: int = 0x5EED, device: int = 0, grid: int = 0):

@@ -54,6 +54,7 @@ def builtin_images() -> dict[str, dict]:
         "rocm/vector-add-hip:latest": {"entrypoint": [_b("rocm-vector-add")]},
         "amdkube/rocm-vector-add:latest": {"entrypoint": [_b("rocm-vector-add")]},
         "amdkube/hbm-probe:latest": {"entrypoint": [_b("hbm-probe")]},
+        "amdkube/hbm-check:latest": {"entrypoint": [_b("hbm-check")]},
         "amdkube/gpu-burn:latest": {"entrypoint": [_b("gpu-burn")]},
         "amdkube/mfma-check:latest": {"entrypoint": [_b("mfma-check")]},
         "amdkube/cu-check:latest": {"entrypoint": [_b("cu-check")]},

@@ -70,9 +70,7 @@ constexpr int CU_CHECK_TRANS_N = CU_CHECK_TRANS_FUNCS * CU_CHECK_TRANS_SETS;  //
 constexpr int CU_CHECK_VALU_OPS = 12;   // dumped operand words per lane: a0 b0 c0 a1 b1 c1 wa wb wc x m k
 constexpr int CU_CHECK_VALU_MADS = 2 + 2 + 2 + 2 + 2 + CU_CHECK_CHAIN;  // multiply-adds per lane and round
 enum : int { CU_UNIT_LDS = 1, CU_UNIT_VALU = 2, CU_UNIT_TRANS = 4, CU_UNIT_ALL = 7 };
-// s_getreg_b32 operand: register id, offset 0, all 32 bits
-constexpr int CU_HWREG_HW_ID = 4 | (31 << 11);
-constexpr int CU_HWREG_XCC_ID = 20 | (31 << 11);
+// (CU_HWREG_HW_ID, CU_HWREG_XCC_ID, CuLocation and cu_decode_location: gpu_common.h, shared with hbm_check.h)
 
 // unit: 0 lds, 1 valu, 2 trans; hw_id and xcc_id are the raw words of the wave that saw the mismatch.
 // lds: index is the LDS byte address and pass the march pass (2, 3 or 4). valu: index is
@@ -464,20 +462,6 @@ __global__ __launch_bounds__(CU_CHECK_THREADS) void cu_check_kernel(CuCheckArgs 
 }
 
 // ---------------------------------------------------------------------------- runners
-struct CuLocation {
-  int xcc = 0, se = 0, sh = 0, cu = 0;
-  uint32_t key() const { return static_cast<uint32_t>(xcc) << 12 | se << 8 | sh << 4 | cu; }
-};
-
-inline CuLocation cu_decode_location(uint32_t hw_id, uint32_t xcc_id) {
-  CuLocation l;
-  l.xcc = xcc_id & 15u;
-  l.cu = (hw_id >> 8) & 15u;
-  l.sh = (hw_id >> 12) & 1u;
-  l.se = (hw_id >> 13) & 7u;
-  return l;
-}
-
 inline int cu_check_blocks(int cu_count) { return (cu_count > 0 ? cu_count : 256) * CU_CHECK_BLOCKS_PER_CU; }
 
 // unit u has the mask bit 1 << u and the number u in a record

@@ -22,6 +22,8 @@
 //   CU check     (cu_check.h) one workgroup per CU with all 160 KiB of LDS: a march over the LDS, the
 //                same multiply-adds on the fp32, packed-fp32, fp64 and integer pipes, the
 //                transcendental unit on two waves, and the XCD / shader engine / CU it ran on
+//   HBM check    (hbm_check.h, behind hbm-check) a MATS++ march on the pattern below over a region planned by
+//                hbm_plan.h: every bit read in both states, every error with its offset, bits and place
 // The host side is shared: gpu_host.h (AK_HIP, DevInfo, DevBuf, GpuTimer), check_core.h (calibration,
 // self-test flip positions, list splitting) and vadd_contract.h (the pod workload's contract, which
 // hsa-vector-add shares: flags, inputs, verification, stream_grid, output lines, exit codes); the last
@@ -70,6 +72,26 @@ __device__ __forceinline__ uint32_t mix32(uint32_t x) {
 // the checks' hash of (seed, workgroup, index)
 __device__ __forceinline__ uint32_t mix32(uint32_t seed, uint32_t block, uint32_t index) {
   return mix32(mix32(seed ^ (0x9e3779b9u * (block + 1))) + index);
+}
+
+// Where a wave runs: the raw HW_ID and XCC_ID words (the field layout and what an MI355X shows in them:
+// cu_check.h) and their decoding into (xcc, se, sh, cu). For the checks that say where an error was seen.
+// s_getreg_b32 operand: register id, offset 0, all 32 bits
+constexpr int CU_HWREG_HW_ID = 4 | (31 << 11);
+constexpr int CU_HWREG_XCC_ID = 20 | (31 << 11);
+
+struct CuLocation {
+  int xcc = 0, se = 0, sh = 0, cu = 0;
+  uint32_t key() const { return static_cast<uint32_t>(xcc) << 12 | se << 8 | sh << 4 | cu; }
+};
+
+inline CuLocation cu_decode_location(uint32_t hw_id, uint32_t xcc_id) {
+  CuLocation l;
+  l.xcc = xcc_id & 15u;
+  l.cu = (hw_id >> 8) & 15u;
+  l.sh = (hw_id >> 12) & 1u;
+  l.se = (hw_id >> 13) & 7u;
+  return l;
 }
 
 __device__ __forceinline__ uint4 pattern(size_t i, uint32_t seed) {

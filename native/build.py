@@ -3,16 +3,16 @@
   python native/build.py            # CPU-side pybind modules + pause (g++), HIP targets (hipcc, gfx950)
   python native/build.py --cpu-only # just the g++ targets (used by the CPU test tier)
   python native/build.py --sanitize # also the ASan/UBSan host builds (pause, topo self-test, sampler, and the check_core,
-                                    # vadd_contract and io_trace self-tests) and the ThreadSanitizer builds of the
+                                    # hbm_plan, vadd_contract and io_trace self-tests) and the ThreadSanitizer builds of the
                                     # activity sampler, the prefetch and the I/O trace
 
 Outputs: amdkube/_native/{_amdsmi,_topo,_kproto,_quantile,_hipops}.<ext> and amdkube/_native/bin/{pause,
-amdkube-nsexec,amdkube-logpump,sysfs-prefetch-selftest,check-core-selftest,vadd-contract-selftest,io-trace-selftest,
-rocm-vector-add,hsa-vector-add,hbm-probe,gpu-burn,mfma-check,cu-check,xgmi-probe[,topo-selftest-asan,
+amdkube-nsexec,amdkube-logpump,sysfs-prefetch-selftest,check-core-selftest,hbm-plan-selftest,vadd-contract-selftest,
+io-trace-selftest,rocm-vector-add,hsa-vector-add,hbm-probe,hbm-check,gpu-burn,mfma-check,cu-check,xgmi-probe[,topo-selftest-asan,
 pause-asan,
 amdkube-nsexec-asan,amdkube-logpump-asan,
 seccomp-check-asan,sampler-selftest-{asan,tsan},sysfs-prefetch-selftest-{asan,tsan},check-core-selftest-asan,
-vadd-contract-selftest-asan,io-trace-selftest-{asan,tsan}]}.
+hbm-plan-selftest-asan,vadd-contract-selftest-asan,io-trace-selftest-{asan,tsan}]}.
 Targets are rebuilt only when a source/header is newer than the output.
 """
 from __future__ import annotations
@@ -50,6 +50,7 @@ def targets(sanitize=False, cpu_only=False):
     n = lambda *p: os.path.join(ROOT, *p)  # noqa: E731
     vadd_selftest = [n("native/vadd_contract_selftest.cpp"), n("kernels/vadd_contract.h")]
     trace_selftest = [n("native/io_trace_selftest.cpp"), n("native/io_trace.h"), n("native/sysfs_prefetch.h")]
+    plan_selftest = [n("native/hbm_plan_selftest.cpp"), n("kernels/hbm_plan.h"), n("kernels/check_core.h")]
     t = [
         (n(OUT, "_topo" + EXT), [n("native/topo_alloc.cpp"), n("native/topo_core.h")],
          ["g++", "-O3", "-std=c++17", "-shared", "-fPIC", *py, n("native/topo_alloc.cpp"), "-o", "{out}"]),
@@ -83,6 +84,8 @@ def targets(sanitize=False, cpu_only=False):
         # the calibration, flip positions and list splitting of the GPU checks, against the loops they replaced
         (n(BIN, "check-core-selftest"), [n("native/check_core_selftest.cpp"), n("kernels/check_core.h")],
          ["g++", "-O2", "-std=c++17", "-Wall", n("native/check_core_selftest.cpp"), "-o", "{out}"]),
+        # hbm-check's region, chunks, offsets, seeds and self-test slots
+        (n(BIN, "hbm-plan-selftest"), plan_selftest, ["g++", "-O2", "-std=c++17", "-Wall", plan_selftest[0], "-o", "{out}"]),
         # the pod workload's contract (flags, inputs, verification, grid, output lines) against the two copies it replaced
         (n(BIN, "vadd-contract-selftest"), vadd_selftest, ["g++", "-O2", "-std=c++17", "-Wall", vadd_selftest[0], "-o", "{out}"]),
         # the I/O trace of hsa-vector-add through the program's own fopen / fclose / open / opendir
@@ -120,6 +123,8 @@ def targets(sanitize=False, cpu_only=False):
               n("native/sysfs_prefetch_selftest.cpp"), "-pthread", "-ldl", "-o", "{out}"]),
             (n(BIN, "check-core-selftest-asan"), [n("native/check_core_selftest.cpp"), n("kernels/check_core.h")],
              ["g++", "-O1", "-std=c++17", *san, n("native/check_core_selftest.cpp"), "-o", "{out}"]),
+            (n(BIN, "hbm-plan-selftest-asan"), plan_selftest,
+             ["g++", "-O1", "-std=c++17", *san, plan_selftest[0], "-o", "{out}"]),
             (n(BIN, "vadd-contract-selftest-asan"), vadd_selftest,
              ["g++", "-O1", "-std=c++17", *san, vadd_selftest[0], "-o", "{out}"]),
             (n(BIN, "io-trace-selftest-asan"), trace_selftest,
@@ -141,8 +146,9 @@ def targets(sanitize=False, cpu_only=False):
         chk = [n("kernels/mfma_check.h"), *base]
         lp = [n("kernels/mfma_check_lp.h"), *chk]
         cu = [n("kernels/cu_check.h"), *base]
+        hbm = [n("kernels/hbm_check.h"), n("kernels/hbm_plan.h"), *base]
         t += [
-            (n(OUT, "_hipops" + EXT), [n("native/hipops.hip"), n("kernels/cu_check.h"), *lp],
+            (n(OUT, "_hipops" + EXT), [n("native/hipops.hip"), n("kernels/cu_check.h"), *hbm[:2], *lp],
              [*ho, "-shared", "-fPIC", *py, n("native/hipops.hip"), "-o", "{out}"]),
             (n(BIN, "rocm-vector-add"), [n("kernels/vector_add.hip"), *base], [*ho, n("kernels/vector_add.hip"), "-o", "{out}"]),
             # the HIP-free pod workload: a bare gfx950 code object, then the HSA host embedding it
@@ -155,6 +161,7 @@ def targets(sanitize=False, cpu_only=False):
               f'-I{ROCM}/include {n("kernels/hsa_vector_add.cpp")} -L{ROCM}/lib -Wl,-rpath,{ROCM}/lib -lhsa-runtime64 -pthread -ldl -o "$1"',
               hip, "{out}"]),
             (n(BIN, "hbm-probe"), [n("kernels/hbm_probe.hip"), *base], [*ho, n("kernels/hbm_probe.hip"), "-o", "{out}"]),
+            (n(BIN, "hbm-check"), [n("kernels/hbm_check.hip"), *hbm], [*ho, n("kernels/hbm_check.hip"), "-o", "{out}"]),
             (n(BIN, "gpu-burn"), [n("kernels/gpu_burn.hip"), *chk], [*ho, n("kernels/gpu_burn.hip"), "-o", "{out}"]),
             (n(BIN, "mfma-check"), [n("kernels/mfma_check.hip"), *lp], [*ho, n("kernels/mfma_check.hip"), "-o", "{out}"]),
             (n(BIN, "cu-check"), [n("kernels/cu_check.hip"), *cu], [*ho, n("kernels/cu_check.hip"), "-o", "{out}"]),

@@ -8,6 +8,7 @@
 #include <pybind11/stl.h>
 
 #include "../kernels/cu_check.h"
+#include "../kernels/hbm_check.h"
 #include "../kernels/mfma_check_lp.h"
 
 namespace py = pybind11;
@@ -92,6 +93,31 @@ static py::dict cu_check_result(const amdkube::CuCheckResult& r) {
   return o;
 }
 
+// the counters and records of an HBM check or of one march launch (kernels/hbm_check.h)
+static void hbm_check_counts(const amdkube::HbmCheckResult& r, const char* records_key, py::dict& o) {
+  py::list recs;
+  for (const amdkube::HbmCheckRecord& e : r.first_errors) {
+    py::dict d = cu_location(amdkube::cu_decode_location(e.hw_id, e.xcc_id));
+    d["round"] = e.round;
+    d["pass"] = e.pass;
+    d["chunk"] = e.chunk;
+    d["slot"] = e.slot;
+    d["word"] = e.word;
+    d["got"] = e.got;
+    d["want"] = e.want;
+    d["again"] = e.again;
+    d["hw_id"] = e.hw_id;
+    d["xcc_id"] = e.xcc_id;
+    recs.append(d);
+  }
+  o["errors"] = r.errors;
+  o["bit_errors"] = r.bit_errors;
+  o["transient"] = r.transient;
+  o["persistent"] = r.persistent;
+  o["records_dropped"] = r.records_dropped;
+  o[records_key] = recs;
+}
+
 template <class T>
 using array_in = py::array_t<T, py::array::c_style | py::array::forcecast>;
 using bytes_in = array_in<uint8_t>;
@@ -115,7 +141,7 @@ static py::tuple tile_tuple(const amdkube::MfmaCheckTile& t) {
 }
 
 PYBIND11_MODULE(_hipops, m) {
-  m.doc() = "amdkube HIP (gfx950) validation kernels: vector add, HBM probe, MFMA burn, MFMA check, CU check";
+  m.doc() = "amdkube HIP (gfx950) validation kernels: vector add, HBM probe, HBM check, MFMA burn, MFMA check, CU check";
   m.def("device_count", []() {
     int n = 0;
     AK_HIP(hipGetDeviceCount(&n));
@@ -304,6 +330,49 @@ PYBIND11_MODULE(_hipops, m) {
         return o;
       },
       py::arg("block"), py::arg("seed") = 0x5eedu, py::arg("device") = 0);
+  // the HBM march (kernels/hbm_check.h): mib == 0 and free_fraction == 0 mean "not given"
+  m.def(
+      "hbm_check",
+      [](long long mib, double free_fraction, long long chunk_mib, int rounds, uint32_t seed, int flips, int hold_ms, int dev) {
+        const amdkube::HbmCheckResult r =
+            nogil([&] { return amdkube::run_hbm_check(mib, free_fraction, chunk_mib, rounds, seed, flips, hold_ms, dev); });
+        py::dict o;
+        py::list bad;
+        for (const amdkube::HbmBadPage& b : r.bad_pages) {
+          py::dict d;
+          d["offset"] = b.offset;
+          d["chunk"] = b.chunk;
+          d["errors"] = b.errors;
+          bad.append(d);
+        }
+        o["ok"] = r.errors == 0;
+        o["bytes"] = r.bytes;
+        o["chunks"] = r.chunks;
+        o["rounds"] = r.rounds;
+        o["hold_ms"] = r.hold_ms;
+        o["ms"] = r.ms;
+        o["alloc_ms"] = r.alloc_ms;
+        o["march_gbps"] = r.march_gbps;
+        hbm_check_counts(r, "first_errors", o);
+        o["bad_pages"] = bad;
+        o["bad_pages_total"] = r.bad_pages_total;
+        return o;
+      },
+      py::arg("mib") = 1024, py::arg("free_fraction") = 0.0, py::arg("chunk_mib") = 1024, py::arg("rounds") = 1,
+      py::arg("seed") = 0x5eedu, py::arg("selftest_flips") = 0, py::arg("hold_ms") = 0, py::arg("device") = 0);
+  m.def(
+      "hbm_march_pass",
+      [](array_in<uint32_t> words, uint32_t seed, uint32_t inv, bool down, bool write, int dev, int grid) {
+        const std::vector<uint32_t> w = to_vec(words);
+        const amdkube::HbmMarchPassResult r = nogil([&] { return amdkube::hbm_march_pass_host(w, seed, inv, down, write, dev, grid); });
+        py::dict o;
+        o["words"] = py::array_t<uint32_t>(r.words.size(), r.words.data());
+        o["page_errors"] = py::array_t<uint32_t>(r.page_errors.size(), r.page_errors.data());
+        hbm_check_counts(r.counts, "records", o);
+        return o;
+      },
+      py::arg("words"), py::arg("seed"), py::arg("inv"), py::arg("down"), py::arg("write"), py::arg("device") = 0,
+      py::arg("grid") = 0);
   m.def(
       "mfma_burn",
       [](double ms, int dev) {
