@@ -12,7 +12,8 @@ plugin's InitContainer response as carried in the CRI ContainerConfig:
            `amdkube-nsexec` launcher (native/devguard.h), strongest mechanism first
            (`isolation=auto` probes the node once, `amdkube-nsexec --probe`):
            `namespaces` (root): a private mount namespace whose /dev/dri holds only the
-                 container's render nodes, /dev/kfd masked for non-GPU containers, a cgroup-v2
+                 container's render nodes, /dev/kfd refused to non-GPU containers (by Landlock,
+                 else masked with /dev/null), a cgroup-v2
                  leaf with cpu/memory limits and a BPF device filter (226:* only the kept
                  minors, kfd only with a GPU), Landlock layered under it, the capability
                  bounding set cut to Docker's default, no_new_privs;
@@ -932,7 +933,7 @@ class RocShim:
                 return c.argv
             return ([self.nsexec_bin, "--no-namespaces"] + join + (["--seccomp", sec] if sec else []) +
                     (["--apparmor", aa] if aa else []) + (["--cpuset", cpuset] if cpuset else []) + ["--"] + c.argv)
-        # (env isolation: the OOM score is applied to the spawned process directly, see start_container)
+        # (without root the OOM score is applied to the spawned process directly, see start_container)
         a = [self.nsexec_bin, "--dev-root", self.dev_root] + join
         if c.resources.get("rootfs"):
             a += ["--rootfs", c.resources["rootfs"], "--rootfs-upper", self._upper_of(c),
@@ -951,7 +952,8 @@ class RocShim:
         a += ["--caps", c.resources.get("caps") or ",".join(DEFAULT_CAPS)]
         if c.resources.get("cpu_shares"):
             a += ["--cpu-weight", str(_shares_to_weight(c.resources["cpu_shares"]))]
-        if c.resources.get("oom_score_adj"):
+        if c.resources.get("oom_score_adj") and self.isolation == "namespaces":
+            # the launcher fails when the kernel refuses the score, and lowering one takes root
             a += ["--oom-score-adj", str(c.resources["oom_score_adj"])]
         if sec:
             a += ["--seccomp", sec]
@@ -967,9 +969,11 @@ class RocShim:
                 a += ["--bind", f"{mnt['host_path']}:{mnt['container_path']}" + (":ro" if mnt.get("readonly") else "")]
         if c.resources.get("rootfs") and c.handler == "rocm":
             # the rocm handler's injection (the nvidia runtime's driver-library hook, re-homed):
-            # the node's ROCm user space, read-only, unless a volume already provides it
+            # the node's ROCm user space, read-only, unless a volume already provides it. /opt/rocm
+            # is a link into a versioned install (/opt/rocm-<version>) whose path the programs built
+            # against it carry as their library search path, so that directory comes along as itself
             taken = {m["container_path"] for m in c.mounts}
-            for host in ROCM_INJECT:
+            for host in dict.fromkeys(p for h in ROCM_INJECT for p in (h, os.path.realpath(h))):
                 if os.path.exists(host) and host not in taken:
                     a += ["--bind", f"{host}:{host}:ro"]
         a += [x for x in self._device_args(c) if x != "--hide-kfd"]

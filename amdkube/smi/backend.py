@@ -147,7 +147,8 @@ class Backend:
 
     def ras(self, index: int) -> dict:
         """RAS state beyond the ECC totals: xgmi_error (0 none, 1 error, 2 multiple),
-        bad_pages{,_retired,_pending,_unreservable}, bad_page_threshold; absent = unknown."""
+        xgmi_links_{up,down}, bad_pages{,_retired,_pending,_unreservable}, bad_page_threshold;
+        absent = unknown."""
         return {}
 
     def start_sampling(self, period_ms: float = 100.0) -> bool:
@@ -178,14 +179,14 @@ class Backend:
 
 
 class AmdSmiBackend(Backend):
-    per_process = True
-
     name = "amdsmi"
 
     def __init__(self):
         from .._native import _amdsmi  # noqa: F401  (fails loudly if the shim was not built)
         self.lib = _amdsmi
         self.lib.init()
+        # a driver without KFD's per-process directory (a VM guest) lists no process at all
+        self.per_process = self.lib.process_accounting()
         self._lock = threading.Lock()
         self._gpus = None
 

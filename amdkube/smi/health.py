@@ -9,9 +9,9 @@ already above a threshold would hide every new error. So the monitor snapshots e
 state when it starts and flags:
 
   * uncorrectable ECC errors above `ecc_threshold` SINCE the snapshot (deferred errors too);
-  * an xGMI error status that was clear at the snapshot, or new uncorrectable errors in the
-    XGMI_WAFL RAS block (link errors: the multi-GPU collectives of a pod placed across this GPU
-    would fail or crawl);
+  * an xGMI error status that was clear at the snapshot, new uncorrectable errors in the
+    XGMI_WAFL RAS block, or an xGMI link that was up at the snapshot and is down now (link
+    errors: the multi-GPU collectives of a pod placed across this GPU would fail or crawl);
   * new pages pending retirement or unreservable (memory the driver could not retire);
   * the bad-page count reaching the driver's bad-page threshold (the RAS EEPROM's limit:
     the part needs service);
@@ -246,6 +246,11 @@ class HealthMonitor:
         dx = cur.get("ras_xgmi_ecc_uncorrectable", 0) - base.get("ras_xgmi_ecc_uncorrectable", 0)
         if dx > self.ecc_threshold:
             return f"xGMI link uncorrectable errors: +{dx} since the plugin started"
+        # the per-link state: the one xGMI source left where the driver exposes neither of the
+        # two above (a VM guest); a link that was down at the snapshot is not a new fault
+        dl = cur.get("ras_xgmi_links_down", 0) - base.get("ras_xgmi_links_down", 0)
+        if dl > 0:
+            return f"{dl} xGMI link(s) went down since the plugin started"
         for k, what in (("bad_pages_pending", "pending retirement"), ("bad_pages_unreservable", "unreservable")):
             d = cur.get(k, 0) - base.get(k, 0)
             if d > 0:

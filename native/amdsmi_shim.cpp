@@ -10,7 +10,8 @@
 //   sample(i)      dynamic metrics (VRAM used, gfx/umc activity, power, temperature, ECC)
 //   topology()     N x N link matrix {type, hops, weight, p2p}
 //   link_metrics(i) per-link xGMI bit rate / bandwidth / read+write KB counters
-//   processes(i)   per-process VRAM and engine time (container GPU accounting)
+//   processes(i)   per-process VRAM and engine time (container GPU accounting), meaningful
+//                  where process_accounting() is true
 //   start_sampler / average_activity / stop_sampler
 //                  background gfx/umc activity sampling (native/sampler_core.h) and its mean
 //                  over a window: gonvml AverageGPUUtilization (bindings.go:218-260), which
@@ -21,6 +22,7 @@
 #include <amd_smi/amdsmi.h>
 #include <pybind11/pybind11.h>
 #include <pybind11/stl.h>
+#include <sys/stat.h>
 
 #include <cstdio>
 #include <cstring>
@@ -209,6 +211,17 @@ py::dict sample(size_t i) {
   {
     py::gil_scoped_release nogil;
     s_used = amdsmi_get_gpu_memory_usage(h, AMDSMI_MEM_TYPE_VRAM, &used);
+    if (s_used != AMDSMI_STATUS_SUCCESS || used == 0) {
+      // that query reads the driver's sysfs counter, and where the file is missing (a VM guest)
+      // it succeeds with 0, which a GPU with a loaded driver never has in use: ask the DRM
+      // device itself (whole MiB)
+      amdsmi_vram_usage_t vu;
+      std::memset(&vu, 0, sizeof(vu));
+      if (amdsmi_get_gpu_vram_usage(h, &vu) == AMDSMI_STATUS_SUCCESS) {
+        used = static_cast<uint64_t>(vu.vram_used) << 20;
+        s_used = AMDSMI_STATUS_SUCCESS;
+      }
+    }
     std::memset(&act, 0, sizeof(act));
     s_act = amdsmi_get_gpu_activity(h, &act);
     std::memset(&pw, 0, sizeof(pw));
@@ -239,8 +252,8 @@ py::dict sample(size_t i) {
   return d;
 }
 
-// RAS state beyond the ECC totals: xGMI error status, retired/pending bad pages, the bad-page
-// threshold and which blocks have ECC enabled. Each query's status is reported (`*_status`)
+// RAS state beyond the ECC totals: xGMI error status and link state, retired/pending bad pages,
+// the bad-page threshold and which blocks have ECC enabled. Each query's status is reported (`*_status`)
 // so callers can tell "no errors" from "not supported here" or "needs root".
 py::dict ras(size_t i) {
   auto h = gpu(i);
@@ -252,6 +265,8 @@ py::dict ras(size_t i) {
   amdsmi_status_t s_x, s_b, s_r, s_t, s_e, s_bb = AMDSMI_STATUS_SUCCESS;
   amdsmi_error_count_t xe;
   amdsmi_status_t s_xe;
+  amdsmi_xgmi_link_status_t xl;
+  amdsmi_status_t s_xl;
   {
     py::gil_scoped_release nogil;
     s_x = amdsmi_gpu_xgmi_error_status(h, &xs);
@@ -266,6 +281,8 @@ py::dict ras(size_t i) {
     s_e = amdsmi_get_gpu_ecc_enabled(h, &ecc_mask);
     std::memset(&xe, 0, sizeof(xe));
     s_xe = amdsmi_get_gpu_ecc_count(h, AMDSMI_GPU_BLOCK_XGMI_WAFL, &xe);
+    std::memset(&xl, 0, sizeof(xl));
+    s_xl = amdsmi_get_gpu_xgmi_link_status(h, &xl);
   }
   auto st = [](amdsmi_status_t s) {
     const char* msg = nullptr;
@@ -297,6 +314,18 @@ py::dict ras(size_t i) {
   if (s_xe == AMDSMI_STATUS_SUCCESS) {
     d["xgmi_ecc_correctable"] = xe.correctable_count;
     d["xgmi_ecc_uncorrectable"] = xe.uncorrectable_count;
+  }
+  // the per-link state of the GPU metrics table: it answers where the driver exposes neither RAS
+  // file above (a VM guest with the GPU passed through)
+  d["xgmi_links_status"] = st(s_xl);
+  if (s_xl == AMDSMI_STATUS_SUCCESS) {
+    int up = 0, down = 0;
+    for (uint32_t k = 0; k < xl.total_links && k < AMDSMI_MAX_NUM_XGMI_LINKS; ++k) {
+      if (xl.status[k] == AMDSMI_XGMI_LINK_UP) ++up;
+      else if (xl.status[k] == AMDSMI_XGMI_LINK_DOWN) ++down;
+    }
+    d["xgmi_links_up"] = up;
+    d["xgmi_links_down"] = down;
   }
   return d;
 }
@@ -374,6 +403,14 @@ py::list link_metrics(size_t i) {
   return out;
 }
 
+// amd-smi builds its process list from KFD's per-process directory. A driver that does not expose
+// it (a VM guest) makes every list come back empty with SUCCESS, which is not "no process holds
+// memory": callers ask here first whether the list means anything.
+bool process_accounting() {
+  struct stat st;
+  return stat("/sys/class/kfd/kfd/proc", &st) == 0 && S_ISDIR(st.st_mode);
+}
+
 py::list processes(size_t i) {
   auto h = gpu(i);
   uint32_t n = 0;
@@ -449,6 +486,7 @@ PYBIND11_MODULE(_amdsmi, m) {
   m.def("topology", &topology);
   m.def("link_metrics", &link_metrics);
   m.def("processes", &processes);
+  m.def("process_accounting", &process_accounting);
   m.def("start_sampler", &start_sampler, py::arg("period_ms") = 100.0, py::arg("capacity") = 1024);
   m.def("stop_sampler", &stop_sampler);
   m.def("average_activity", &average_activity, py::arg("index"), py::arg("window_s") = 10.0);

@@ -62,13 +62,16 @@ def test_01b_ras_queries_and_new_fault_health():
         print("ras:", r)
         ok_states = ("SUCCESS", "NOT_SUPPORTED", "NO_PERM", "NOT_YET_IMPLEMENTED", "FILE_ERROR")
         for k in ("bad_pages_status", "reserved_pages_status", "bad_page_threshold_status", "ecc_enabled_status",
-                  "xgmi_ecc_status"):
+                  "xgmi_ecc_status", "xgmi_links_status"):
             assert any(st in r[k] for st in ok_states), (k, r[k])
-        # xGMI health has two sources; the error-status file answers INVAL on the gpurun box, the
-        # XGMI_WAFL RAS block counts answer: at least one must
-        assert "xgmi_error" in r or "xgmi_ecc_uncorrectable" in r, r
+        # xGMI health has three sources; where the error-status file answers INVAL on bare metal, the
+        # XGMI_WAFL RAS block counts answer; a VM guest has neither RAS file, and there the
+        # per-link state answers: at least one must
+        assert "xgmi_error" in r or "xgmi_ecc_uncorrectable" in r or "xgmi_links_down" in r, r
         if "xgmi_error" in r:
             assert r["xgmi_error"] in (0, 1, 2)
+        if "xgmi_links_down" in r:
+            assert 0 <= r["xgmi_links_down"] <= 8 and 0 <= r["xgmi_links_up"] <= 8, r
         assert "bad_pages" in r or "reserved_pages" in r, r
         hm = HealthMonitor(b)
         hm.snapshot(0)
@@ -154,10 +157,12 @@ def test_02d_rootfs_image_pod_on_mi355x(tmp_path):
     from amdkube.runtime.oci import write_docker_archive
     vadd = os.path.join(BIN, "rocm-vector-add")
     files = {vadd: "usr/local/bin/rocm-vector-add"}
-    for line in sp.run(["ldd", vadd], capture_output=True, text=True, check=True).stdout.splitlines():
-        for tok in line.split():
-            if tok.startswith("/") and os.path.exists(tok) and not tok.startswith("/opt/rocm"):
-                files[tok] = tok.lstrip("/")
+    # the closure of the program and of the code object manager, which HIP loads only at run time
+    for binary in (vadd, "/opt/rocm/lib/libamd_comgr.so"):
+        for line in sp.run(["ldd", binary], capture_output=True, text=True, check=True).stdout.splitlines():
+            for tok in line.split():
+                if tok.startswith("/") and os.path.exists(tok) and not tok.startswith("/opt/rocm"):
+                    files[tok] = tok.lstrip("/")
     entries, dirs = [], set()
     for src, rel in sorted(files.items(), key=lambda kv: kv[1]):
         d = os.path.dirname(rel)

@@ -51,6 +51,18 @@ def test_xgmi_block_errors_when_the_status_file_is_unreadable():
     assert hm.check(0) == (False, "xGMI link uncorrectable errors: +1 since the plugin started")
 
 
+def test_xgmi_link_state_when_neither_ras_file_answers():
+    fb = FakeBackend(n=1)
+    hm = HealthMonitor(fb)
+    fb.ras(0)
+    fb.ras_state[0].pop("xgmi_error")
+    fb.ras_state[0].update(xgmi_links_up=6, xgmi_links_down=1)   # one link was down all along
+    hm.snapshot(0)
+    assert hm.check(0) == (True, "")
+    fb.ras_state[0].update(xgmi_links_up=4, xgmi_links_down=3)
+    assert hm.check(0) == (False, "2 xGMI link(s) went down since the plugin started")
+
+
 def test_ecc_threshold_allows_a_budget():
     fb = FakeBackend(n=1)
     hm = HealthMonitor(fb, ecc_threshold=2)

@@ -113,6 +113,45 @@ def test_unguarded_launch_sees_everything(fake_dev):
     assert r["renderD128"] == "ok" and r["kfd"] == "ok" and r["proc_root"] == "ok"
 
 
+@needs_landlock
+@pytest.mark.needs_root          # a mount namespace
+def test_private_dev_with_landlock_refuses_kfd_to_a_non_gpu_container(fake_dev):
+    """The namespace modes' launch line: a private, empty /dev/dri, and kfd itself refused by the
+    guard (no /dev/null in its place, which would open)."""
+    p = subprocess.run([NSEXEC, "--dev-root", fake_dev, "--landlock", "--hide-kfd", "--", sys.executable, "-c", OPEN_ALL, fake_dev],
+                       capture_output=True, text=True, timeout=30)
+    if p.returncode == 126 and "unshare" in p.stderr:
+        pytest.skip("unshare not permitted in this container")
+    assert p.returncode == 0, p.stderr
+    res = json.loads(p.stdout.strip().splitlines()[-1])
+    assert res["kfd"] == "Permission denied" and res["mknod"] == "Permission denied", res
+    assert not [k for k in res if k.startswith(("renderD", "card"))], res
+
+
+def test_launch_line_without_root(tmp_path, monkeypatch):
+    """isolation=userns: the OOM score is not the launcher's to set (lowering one takes root, and
+    the launcher fails on a refusal); an image container of the rocm handler gets the versioned
+    ROCm directory behind the /opt/rocm link too, even when a volume provides /opt/rocm."""
+    from amdkube.runtime import rocshim
+    from amdkube.runtime.rocshim import Container
+    (tmp_path / "rocm-9.9.9" / "lib").mkdir(parents=True)
+    link = tmp_path / "rocm"
+    link.symlink_to("rocm-9.9.9")
+    monkeypatch.setattr(rocshim, "ROCM_INJECT", (str(link),))
+    argv = {}
+    for mode in ("userns", "namespaces"):
+        shim = RocShim(str(tmp_path / f"{mode}.sock"), str(tmp_path / mode), hooks_dir=str(tmp_path / "hooks"), isolation=mode)
+        c = Container("c1", "s1", "vadd", 0, "img", "img", ["/bin/vadd"], {}, "/", str(tmp_path / "0.log"), {}, {},
+                      [{"container_path": str(link), "host_path": str(link), "readonly": True}], [], "rocm",
+                      {"rootfs": str(tmp_path / "root"), "oom_score_adj": -998, "caps": "default"})
+        argv[mode] = shim._launch_argv(c)
+    assert "--oom-score-adj" not in argv["userns"]
+    assert argv["namespaces"][argv["namespaces"].index("--oom-score-adj") + 1] == "-998"
+    real = str(tmp_path / "rocm-9.9.9")
+    binds = [argv["userns"][i + 1] for i, a in enumerate(argv["userns"]) if a == "--bind"]
+    assert binds == [f"{link}:{link}:ro", f"{real}:{real}:ro"], binds
+
+
 def test_isolation_resolution_order():
     full = {"root": True, "cgroup2_writable": True, "userns": True, "landlock_abi": 7}
     assert resolve_isolation("auto", full) == "namespaces"
