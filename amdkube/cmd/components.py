@@ -908,6 +908,16 @@ def device_plugin_parser():
     ap.add_argument("--hbm-check-mib", default=0, type=mib, metavar="N",
                     help="also march N MiB of every GPU's HBM (hbm-check --mib N: every bit read in both states, errors "
                          "with their offset and 2 MiB page) after the --health-probe list, or alone with none; 0: off")
+    def mfma_dtypes(spec):
+        from ..deviceplugin.amd import parse_mfma_check_dtype
+        try:
+            return parse_mfma_check_dtype(spec)
+        except ValueError as e:
+            raise argparse.ArgumentTypeError(str(e))
+    ap.add_argument("--mfma-check-dtype", default="", type=mfma_dtypes, metavar="LIST",
+                    help="also run the matrix-core check on a comma list of dtypes (mfma-check --dtype LIST --ms 200; "
+                         "fp64,int8 covers the FP64 and the integer matrix paths, which no --health-probe entry does) after "
+                         "the --health-probe list and before --hbm-check-mib, or alone with none; empty: off")
     ap.add_argument("--max-gpus", type=int, default=None, help="advertise only the first N physical GPUs")
     ap.add_argument("--resource-naming", default="single", choices=("single", "mixed"),
                     help="partitioned GPUs: single=amd.com/gpu for all, mixed=amd.com/<cpx>_<nps> per partition type")
@@ -940,7 +950,8 @@ def device_plugin(argv):
         backend = open_backend(a.backend, a.fixture, a.max_gpus, a.partition)
         plugins = make_plugins(backend, a.resource_naming, a.resource_name, plugins_dir=a.plugins_dir,
                                health_interval=a.health_interval, health_probe=a.health_probe,
-                               health_state=state or None, hbm_check_mib=a.hbm_check_mib)
+                               health_state=state or None, hbm_check_mib=a.hbm_check_mib,
+                               mfma_check_dtype=a.mfma_check_dtype)
         for p in plugins:
             await p.start()
             if a.register_v1beta1:

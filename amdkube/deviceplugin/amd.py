@@ -172,6 +172,25 @@ def hbm_check_timeout(mib: int) -> float:
     return HBM_CHECK_BASE_S + HBM_CHECK_S_PER_GIB * mib / 1024.0
 
 
+# Nor is the matrix-core check of further dtypes: `--mfma-check-dtype LIST` runs `mfma-check --dtype LIST
+# --ms 200` on every GPU after the probe list and before the HBM march (also when the list is `none`). It is
+# how the FP64 and INT8 matrix paths (fp64, int8: kernels/mfma_check_wide.h) are checked; LIST is any comma
+# list over the names mfma-check --dtype takes.
+MFMA_CHECK_DTYPES = ("bf16", "fp8", "mxfp8", "mxfp4", "fp64", "int8")
+
+
+def parse_mfma_check_dtype(spec: str) -> str:
+    """`` (off), or a comma list over MFMA_CHECK_DTYPES → the list as mfma-check --dtype takes it."""
+    if not str(spec):
+        return ""
+    names = [p.strip() for p in str(spec).split(",")]
+    bad = [p for p in names if p not in MFMA_CHECK_DTYPES]
+    if bad:
+        raise ValueError(f"unknown mfma-check dtype {bad[0]!r} in {spec!r}: expected a comma list of "
+                         f"{', '.join(MFMA_CHECK_DTYPES)}")
+    return ",".join(names)
+
+
 def parse_health_probe(spec: str) -> list[str]:
     """`none`, or a comma list over all_health_probes() → the probes to run, HBM first."""
     known = all_health_probes()
@@ -189,8 +208,10 @@ class AMDGPUPlugin(DevicePluginServer):
     def __init__(self, backend: Backend, resource_name: str = RESOURCE, plugins_dir: str = DEVICE_PLUGINS_PATH,
                  health_interval: float = 10.0, health_probe: str = "none", dev_root: str = "/dev",
                  ecc_threshold: int = 0, expose_card: bool = True, init_timeout: int = 10,
-                 devices: list[dict] | None = None, health_state: str | None = None, hbm_check_mib: int = 0):
+                 devices: list[dict] | None = None, health_state: str | None = None, hbm_check_mib: int = 0,
+                 mfma_check_dtype: str = ""):
         super().__init__(resource_name, plugins_dir, init_timeout)
+        self.mfma_check_dtype = parse_mfma_check_dtype(mfma_check_dtype)
         if hbm_check_mib < 0:
             raise ValueError("hbm_check_mib must not be negative (0: no HBM march)")
         self.hbm_check_mib = int(hbm_check_mib)
@@ -228,7 +249,7 @@ class AMDGPUPlugin(DevicePluginServer):
     async def start(self):
         for g in self.gpus:             # the RAS baseline new faults are judged against
             self.monitor.snapshot(g["index"])
-        if self.probes or self.hbm_check_mib:
+        if self.probes or self.hbm_check_mib or self.mfma_check_dtype:
             await self._probe_all()
         self._check_health(push=False)
         await super().start()
@@ -300,11 +321,13 @@ class AMDGPUPlugin(DevicePluginServer):
                 log.error("health check failed: %s", e)
 
     async def _probe_all(self):
-        """Run the configured on-device probes (HBM pattern, matrix-core checks, per-CU check, then the HBM
-        march if hbm_check_mib is set) on each GPU (subprocess → isolated HIP context); the first failure
+        """Run the configured on-device probes (HBM pattern, matrix-core checks, per-CU check, then the
+        matrix-core check of mfma_check_dtype and the HBM march of hbm_check_mib, where set) on each GPU (subprocess → isolated HIP context); the first failure
         takes the GPU out of service and ends its chain."""
         known = all_health_probes()
         runs = [(*known[probe], 60) for probe in self.probes]
+        if self.mfma_check_dtype:
+            runs.append(("mfma-check", ["--dtype", self.mfma_check_dtype, "--ms", "200"], 60))
         if self.hbm_check_mib:
             runs.append(("hbm-check", ["--mib", str(self.hbm_check_mib)], hbm_check_timeout(self.hbm_check_mib)))
         for g in self.gpus:

@@ -143,9 +143,46 @@ def mfma_gemm_mx(a_codes, a_scales, b_codes, b_scales, fmt: str, device: int = 0
                     _codes(b_scales, "B scales"), device)
 
 
+WIDE_DTYPES = ("fp64", "int8")            # the FP64 and INT8 matrix-core paths (kernels/mfma_check_wide.h)
+
+
+def _gemm_wide_shapes(a, b, kstep):
+    if a.ndim != 2 or b.ndim != 2 or a.shape[1] != b.shape[0]:
+        raise ValueError(f"need A MxK and B KxN, got {a.shape} and {b.shape}")
+    m, k, n = a.shape[0], a.shape[1], b.shape[1]
+    if m <= 0 or n <= 0 or m % 64 or n % 64 or k <= 0 or k % kstep:
+        raise ValueError(f"need M and N multiples of 64 and K a multiple of {kstep}, got M={m} N={n} K={k}")
+    return m, n, k
+
+
+def mfma_gemm_fp64(a, b, device: int = 0):
+    """C = A @ B with the LDS-staged 64×64 tile kernel on v_mfma_f64_16x16x4_f64: A is M×K, B is K×N,
+    M and N multiples of 64, K a multiple of 4; fp64 in, the result is a float64 tensor."""
+    import numpy as np
+    import torch
+    a, b = _np(a, np.float64), _np(b, np.float64)
+    m, n, k = _gemm_wide_shapes(a, b, 4)
+    return torch.from_numpy(np.asarray(_need().mfma_gemm_fp64(a.ravel(), b.ravel(), m, n, k, device)).copy())
+
+
+def mfma_gemm_int8(a, b, device: int = 0):
+    """C = A @ B with the LDS-staged 64×64 tile kernel on v_mfma_i32_32x32x32_i8: A is M×K, B is K×N,
+    M and N multiples of 64, K a multiple of 32; the inputs are integers in [-128, 127] of any dtype
+    (anything else is a ValueError), the result is an int32 tensor."""
+    import numpy as np
+    import torch
+    a, b = _np(a, None), _np(b, None)
+    for x in (a, b):
+        if x.size and (not np.array_equal(x, np.rint(x)) or x.min() < -128 or x.max() > 127):
+            raise ValueError("int8 operands must be integers in [-128, 127]")
+    m, n, k = _gemm_wide_shapes(a, b, 32)
+    c = _need().mfma_gemm_int8(a.astype(np.int8).ravel(), b.astype(np.int8).ravel(), m, n, k, device)
+    return torch.from_numpy(np.asarray(c).copy())
+
+
 def _check_dtype(dtype):
-    if dtype != "bf16" and dtype not in LP_DTYPES:
-        raise ValueError(f"unknown dtype {dtype!r}: expected bf16, {', '.join(LP_DTYPES)}")
+    if dtype != "bf16" and dtype not in LP_DTYPES and dtype not in WIDE_DTYPES:
+        raise ValueError(f"unknown dtype {dtype!r}: expected bf16, {', '.join(LP_DTYPES + WIDE_DTYPES)}")
 
 
 def mfma_check(rounds: int | None = None, ms: float = 50.0, device: int = 0, seed: int = 0x5EED,
@@ -154,7 +191,9 @@ def mfma_check(rounds: int | None = None, ms: float = 50.0, device: int = 0, see
     compared with exact integer arithmetic in round 0 and bitwise with round 0 afterwards. `rounds`
     runs exactly that many, otherwise the run is calibrated to ~`ms`. `selftest_flips` perturbs
     that many compared values, which the check must then report. `dtype` picks the matrix-core path:
-    bf16, fp8, mxfp8 or mxfp4; the result carries `dtype` and `tflops` (bf16 also `bf16_tflops`)."""
+    bf16, fp8, mxfp8, mxfp4, fp64 or int8; the result carries `dtype` and `tflops` (bf16 also
+    `bf16_tflops`). For int8 `tflops` counts integer operations, 1e12 a second, and for fp64 a record's
+    `got` and `want` are the 32-bit half of the value that differs, the low one if both do."""
     _check_dtype(dtype)
     if rounds is not None and rounds < 1:
         raise ValueError("rounds must be at least 1")
@@ -169,12 +208,16 @@ def mfma_check(rounds: int | None = None, ms: float = 50.0, device: int = 0, see
 
 def mfma_check_tile(block: int, seed: int = 0x5EED, device: int = 0, dtype: str = "bf16"):
     """(A, B, C) of one workgroup of the check: its hashed 64×K and K×64 operands (decoded, with the
-    block scales applied for the MX dtypes) and the 64×64 round-0 MFMA result, as fp32 tensors."""
+    block scales applied for the MX dtypes) and the 64×64 round-0 MFMA result, as fp32 tensors, or
+    as float64 tensors for fp64 and int8, which holds every value of either exactly."""
     import numpy as np
     import torch
     _check_dtype(dtype)
     ext = _need()
-    t = ext.mfma_check_tile(block, seed, device) if dtype == "bf16" else ext.mfma_check_lp_tile(dtype, block, seed, device)
+    if dtype == "bf16":
+        t = ext.mfma_check_tile(block, seed, device)
+    else:
+        t = (ext.mfma_check_wide_tile if dtype in WIDE_DTYPES else ext.mfma_check_lp_tile)(dtype, block, seed, device)
     return tuple(torch.from_numpy(np.asarray(x).copy()) for x in t)
 
 

@@ -240,8 +240,9 @@ struct MfmaCheckResult {
 // Device buffers of one check and the launch of its format; errors and records accumulate over launches.
 struct MfmaCheckRun {
   // queues one launch of a format's check kernel on the run's buffers
-  using Kernel = void (*)(const MfmaCheckRun& run, int rounds, int flips, int dbg_block, float* dbg_a, float* dbg_b,
-                          float* dbg_c);
+  // (the dump pointers are fp32 for the formats of this header and of mfma_check_lp.h, fp64 for mfma_check_wide.h)
+  using Kernel = void (*)(const MfmaCheckRun& run, int rounds, int flips, int dbg_block, void* dbg_a, void* dbg_b,
+                          void* dbg_c);
   int blocks, k;
   uint32_t seed;
   Kernel kernel;
@@ -252,18 +253,19 @@ struct MfmaCheckRun {
         errors(sizeof(unsigned long long), DevBuf::zeroed), nrec(sizeof(unsigned), DevBuf::zeroed),
         recs(MFMA_CHECK_RECORDS * sizeof(MfmaCheckRecord), DevBuf::zeroed),
         flip_pos(flip_positions(seed_, MFMA_CHECK_MAX_FLIPS, static_cast<unsigned long long>(blocks) * (MFMA_TILE * MFMA_TILE))) {}
-  void launch(int rounds, int flips, int dbg_block = -1, float* dbg_a = nullptr, float* dbg_b = nullptr,
-              float* dbg_c = nullptr) const {
+  void launch(int rounds, int flips, int dbg_block = -1, void* dbg_a = nullptr, void* dbg_b = nullptr,
+              void* dbg_c = nullptr) const {
     kernel(*this, rounds, flips, dbg_block, dbg_a, dbg_b, dbg_c);
     AK_HIP(hipGetLastError());
   }
 };
 
-inline void mfma_check_launch_bf16(const MfmaCheckRun& run, int rounds, int flips, int dbg_block, float* dbg_a, float* dbg_b,
-                                   float* dbg_c) {
+inline void mfma_check_launch_bf16(const MfmaCheckRun& run, int rounds, int flips, int dbg_block, void* dbg_a, void* dbg_b,
+                                   void* dbg_c) {
   hipLaunchKernelGGL(mfma_check_kernel, dim3(run.blocks), dim3(256), 0, 0, run.seed, run.k, rounds, flips,
                      run.flip_pos.as<const uint32_t>(), run.errors.as<unsigned long long>(), run.nrec.as<unsigned>(),
-                     run.recs.as<MfmaCheckRecord>(), dbg_block, dbg_a, dbg_b, dbg_c);
+                     run.recs.as<MfmaCheckRecord>(), dbg_block, static_cast<float*>(dbg_a), static_cast<float*>(dbg_b),
+                     static_cast<float*>(dbg_c));
 }
 
 // One check of `kernel`'s format at K = k. rounds > 0: one launch of exactly that many rounds.
@@ -298,20 +300,23 @@ inline MfmaCheckResult run_mfma_check(int rounds, double target_ms, int dev, uin
   return mfma_check_drive(mfma_check_launch_bf16, mfma_check_bf16_k(k_total), rounds, target_ms, dev, seed, flips);
 }
 
-struct MfmaCheckTile {
+template <class V>
+struct MfmaCheckTileOf {
   int k = 0;
-  std::vector<float> a, b, c;  // A[64 x k], B[k x 64], round-0 C[64 x 64] of one workgroup
+  std::vector<V> a, b, c;  // A[64 x k], B[k x 64], round-0 C[64 x 64] of one workgroup
 };
+using MfmaCheckTile = MfmaCheckTileOf<float>;
 
-// one launch of a single round with workgroup `block` storing its operands and product
-inline MfmaCheckTile mfma_check_fetch_tile(MfmaCheckRun::Kernel kernel, int k, int block, uint32_t seed, int dev) {
+// one launch of a single round with workgroup `block` storing its operands and product as V, the type `kernel` dumps
+template <class V = float>
+inline MfmaCheckTileOf<V> mfma_check_fetch_tile(MfmaCheckRun::Kernel kernel, int k, int block, uint32_t seed, int dev) {
   AK_HIP(hipSetDevice(dev));
   MfmaCheckRun run(dev, seed, k, kernel);
   if (block < 0 || block >= run.blocks) throw std::invalid_argument("block out of range");
   const size_t nab = static_cast<size_t>(MFMA_TILE) * k, nc = static_cast<size_t>(MFMA_TILE) * MFMA_TILE;
-  DevBuf da(nab * sizeof(float)), db(nab * sizeof(float)), dc(nc * sizeof(float));
-  run.launch(1, 0, block, da.as<float>(), db.as<float>(), dc.as<float>());
-  return MfmaCheckTile{k, da.download<float>(), db.download<float>(), dc.download<float>()};
+  DevBuf da(nab * sizeof(V)), db(nab * sizeof(V)), dc(nc * sizeof(V));
+  run.launch(1, 0, block, da.p, db.p, dc.p);
+  return MfmaCheckTileOf<V>{k, da.download<V>(), db.download<V>(), dc.download<V>()};
 }
 
 inline MfmaCheckTile mfma_check_tile_host(int block, uint32_t seed, int dev, int k_total = MFMA_CHECK_KMAX) {

@@ -6,13 +6,14 @@
 // otherwise the run is calibrated to ~D ms (default 200). --selftest-flips perturbs N compared
 // values to prove the checker reports them. Prints one JSON line; exit 1 on any mismatch.
 // --dtype takes a comma list over bf16, fp8, mxfp8 and mxfp4 (the FP8 MFMA and the block-scaled
-// e4m3 / e2m1 forms, kernels/mfma_check_lp.h): one JSON line per dtype in the order given, each
+// e4m3 / e2m1 forms, kernels/mfma_check_lp.h), fp64 and int8 (the FP64 and the integer matrix paths,
+// kernels/mfma_check_wide.h; "tflops" counts integer operations for int8): one JSON line per dtype in the order given, each
 // with "dtype" and "tflops", stopping after the first dtype with mismatches; the other flags apply
 // to each dtype. Exit 2 on an unknown dtype, 4 on a runtime error.
 #include <cstdlib>
 #include <cstring>
 
-#include "mfma_check_lp.h"
+#include "mfma_check_wide.h"
 
 static void print_errors(const amdkube::MfmaCheckResult& r) {
   std::printf("\"errors\":%llu,\"first_errors\":[", r.errors);
@@ -41,9 +42,9 @@ int main(int argc, char** argv) {
   std::vector<int> fmts;
   for (const std::string& name : amdkube::split_list(dtypes ? dtypes : "bf16")) {
     try {
-      fmts.push_back(amdkube::mfma_lp_fmt(name, amdkube::MFMA_BF16));
+      fmts.push_back(amdkube::mfma_check_fmt(name, amdkube::MFMA_BF16));
     } catch (const std::invalid_argument&) {
-      std::fprintf(stderr, "mfma-check: unknown dtype '%s': expected a comma list over bf16, fp8, mxfp8, mxfp4\n",
+      std::fprintf(stderr, "mfma-check: unknown dtype '%s': expected a comma list over bf16, fp8, mxfp8, mxfp4, fp64, int8\n",
                    name.c_str());
       return 2;
     }
@@ -51,9 +52,9 @@ int main(int argc, char** argv) {
   try {
     amdkube::DevInfo d = amdkube::dev_info(dev);
     for (int f : fmts) {
-      amdkube::MfmaCheckResult r = amdkube::run_mfma_check_lp(f, rounds, ms, dev, seed, flips);
+      amdkube::MfmaCheckResult r = amdkube::run_mfma_check_fmt(f, rounds, ms, dev, seed, flips);
       std::printf("{\"device\":%d,\"uuid\":\"%s\",\"arch\":\"%s\",", dev, d.uuid.c_str(), d.arch.c_str());
-      if (dtypes) std::printf("\"dtype\":\"%s\",", amdkube::mfma_lp_name(f));
+      if (dtypes) std::printf("\"dtype\":\"%s\",", amdkube::mfma_check_fmt_ops(f).name);
       std::printf("\"blocks\":%d,\"rounds\":%lld,\"k\":%d,\"ms\":%.2f,", r.blocks, r.rounds, r.k, r.ms);
       if (f == amdkube::MFMA_BF16) std::printf("\"bf16_tflops\":%.1f,", r.tflops);
       if (dtypes) std::printf("\"tflops\":%.1f,", r.tflops);

@@ -26,7 +26,8 @@
 namespace amdkube {
 
 // MFMA_BF16 is the check of mfma_check.h, so that one list of formats serves mfma-check; it has no GEMM here
-enum MfmaLpFmt { MFMA_LP_FP8 = 0, MFMA_LP_MXFP8 = 1, MFMA_LP_MXFP4 = 2, MFMA_BF16 = 3 };
+// the two after it are the formats of mfma_check_wide.h, which no table or default of this header reaches
+enum MfmaLpFmt { MFMA_LP_FP8 = 0, MFMA_LP_MXFP8 = 1, MFMA_LP_MXFP4 = 2, MFMA_BF16 = 3, MFMA_WIDE_FP64 = 4, MFMA_WIDE_INT8 = 5 };
 
 typedef int lp_v4i __attribute__((ext_vector_type(4)));
 typedef int lp_v8i __attribute__((ext_vector_type(8)));
@@ -338,11 +339,12 @@ __global__ __launch_bounds__(256, 4) void mfma_check_lp_kernel(uint32_t seed, in
 
 // ---------------------------------------------------------------------------- runners
 template <int F>
-inline void mfma_check_lp_launch(const MfmaCheckRun& run, int rounds, int flips, int dbg_block, float* dbg_a, float* dbg_b,
-                                 float* dbg_c) {
+inline void mfma_check_lp_launch(const MfmaCheckRun& run, int rounds, int flips, int dbg_block, void* dbg_a, void* dbg_b,
+                                 void* dbg_c) {
   hipLaunchKernelGGL(mfma_check_lp_kernel<F>, dim3(run.blocks), dim3(256), 0, 0, run.seed, rounds, flips,
                      run.flip_pos.as<const uint32_t>(), run.errors.as<unsigned long long>(), run.nrec.as<unsigned>(),
-                     run.recs.as<MfmaCheckRecord>(), dbg_block, dbg_a, dbg_b, dbg_c);
+                     run.recs.as<MfmaCheckRecord>(), dbg_block, static_cast<float*>(dbg_a), static_cast<float*>(dbg_b),
+                     static_cast<float*>(dbg_c));
 }
 
 // What a format runs on: its name, its check (launch and K) and its GEMM kernel.

@@ -145,10 +145,11 @@ def targets(sanitize=False, cpu_only=False):
         base = [n("kernels/gpu_common.h"), n("kernels/gpu_host.h"), n("kernels/check_core.h"), n("kernels/vadd_contract.h")]
         chk = [n("kernels/mfma_check.h"), *base]
         lp = [n("kernels/mfma_check_lp.h"), *chk]
+        wide = [n("kernels/mfma_check_wide.h"), *lp]
         cu = [n("kernels/cu_check.h"), *base]
         hbm = [n("kernels/hbm_check.h"), n("kernels/hbm_plan.h"), *base]
         t += [
-            (n(OUT, "_hipops" + EXT), [n("native/hipops.hip"), n("kernels/cu_check.h"), *hbm[:2], *lp],
+            (n(OUT, "_hipops" + EXT), [n("native/hipops.hip"), n("kernels/cu_check.h"), *hbm[:2], *wide],
              [*ho, "-shared", "-fPIC", *py, n("native/hipops.hip"), "-o", "{out}"]),
             (n(BIN, "rocm-vector-add"), [n("kernels/vector_add.hip"), *base], [*ho, n("kernels/vector_add.hip"), "-o", "{out}"]),
             # the HIP-free pod workload: a bare gfx950 code object, then the HSA host embedding it
@@ -163,7 +164,7 @@ def targets(sanitize=False, cpu_only=False):
             (n(BIN, "hbm-probe"), [n("kernels/hbm_probe.hip"), *base], [*ho, n("kernels/hbm_probe.hip"), "-o", "{out}"]),
             (n(BIN, "hbm-check"), [n("kernels/hbm_check.hip"), *hbm], [*ho, n("kernels/hbm_check.hip"), "-o", "{out}"]),
             (n(BIN, "gpu-burn"), [n("kernels/gpu_burn.hip"), *chk], [*ho, n("kernels/gpu_burn.hip"), "-o", "{out}"]),
-            (n(BIN, "mfma-check"), [n("kernels/mfma_check.hip"), *lp], [*ho, n("kernels/mfma_check.hip"), "-o", "{out}"]),
+            (n(BIN, "mfma-check"), [n("kernels/mfma_check.hip"), *wide], [*ho, n("kernels/mfma_check.hip"), "-o", "{out}"]),
             (n(BIN, "cu-check"), [n("kernels/cu_check.hip"), *cu], [*ho, n("kernels/cu_check.hip"), "-o", "{out}"]),
             (n(BIN, "xgmi-probe"), [n("kernels/xgmi_probe.cpp")],
              [*ho, "-x", "hip", n("kernels/xgmi_probe.cpp"), *rocm_inc, *rpath, "-lrccl", "-o", "{out}"]),

@@ -9,7 +9,7 @@
 
 #include "../kernels/cu_check.h"
 #include "../kernels/hbm_check.h"
-#include "../kernels/mfma_check_lp.h"
+#include "../kernels/mfma_check_wide.h"
 
 namespace py = pybind11;
 
@@ -133,11 +133,12 @@ static auto nogil(F&& fn) {
   return fn();
 }
 
-// (A, B, C) of one workgroup of a matrix-core check
-static py::tuple tile_tuple(const amdkube::MfmaCheckTile& t) {
-  return py::make_tuple(py::array_t<float>({amdkube::MFMA_TILE, t.k}, t.a.data()),
-                        py::array_t<float>({t.k, amdkube::MFMA_TILE}, t.b.data()),
-                        py::array_t<float>({amdkube::MFMA_TILE, amdkube::MFMA_TILE}, t.c.data()));
+// (A, B, C) of one workgroup of a matrix-core check: float32 arrays, float64 for the wide dtypes
+template <class V>
+static py::tuple tile_tuple(const amdkube::MfmaCheckTileOf<V>& t) {
+  return py::make_tuple(py::array_t<V>({amdkube::MFMA_TILE, t.k}, t.a.data()),
+                        py::array_t<V>({t.k, amdkube::MFMA_TILE}, t.b.data()),
+                        py::array_t<V>({amdkube::MFMA_TILE, amdkube::MFMA_TILE}, t.c.data()));
 }
 
 PYBIND11_MODULE(_hipops, m) {
@@ -273,7 +274,8 @@ PYBIND11_MODULE(_hipops, m) {
         return tile_tuple(nogil([&] { return amdkube::mfma_check_tile_host(block, seed, dev); }));
       },
       py::arg("block"), py::arg("seed") = 0x5eedu, py::arg("device") = 0);
-  // the low-precision matrix-core paths (kernels/mfma_check_lp.h): dtype is fp8, mxfp8 or mxfp4
+  // the low-precision matrix-core paths (kernels/mfma_check_lp.h): dtype is fp8, mxfp8 or mxfp4;
+  // mfma_check_lp also takes the wide dtypes fp64 and int8 (kernels/mfma_check_wide.h)
   m.def(
       "mfma_gemm_lp",
       [](const std::string& dtype, bytes_in a_codes, bytes_in b_codes, bytes_in a_scales, bytes_in b_scales, int mm, int nn,
@@ -288,8 +290,8 @@ PYBIND11_MODULE(_hipops, m) {
   m.def(
       "mfma_check_lp",
       [](const std::string& dtype, int rounds, double ms, int dev, uint32_t seed, int flips) {
-        const int fmt = amdkube::mfma_lp_fmt(dtype);
-        py::dict o = check_result(nogil([&] { return amdkube::run_mfma_check_lp(fmt, rounds, ms, dev, seed, flips); }), "tflops");
+        const int fmt = amdkube::mfma_check_fmt(dtype);
+        py::dict o = check_result(nogil([&] { return amdkube::run_mfma_check_fmt(fmt, rounds, ms, dev, seed, flips); }), "tflops");
         o["dtype"] = dtype;
         return o;
       },
@@ -300,6 +302,30 @@ PYBIND11_MODULE(_hipops, m) {
       [](const std::string& dtype, int block, uint32_t seed, int dev) {
         const int fmt = amdkube::mfma_lp_fmt(dtype);
         return tile_tuple(nogil([&] { return amdkube::mfma_check_lp_tile_host(fmt, block, seed, dev); }));
+      },
+      py::arg("dtype"), py::arg("block"), py::arg("seed") = 0x5eedu, py::arg("device") = 0);
+  // the FP64 and INT8 matrix-core paths (kernels/mfma_check_wide.h)
+  m.def(
+      "mfma_gemm_fp64",
+      [](array_in<double> a, array_in<double> b, int mm, int nn, int k, int dev) {
+        const std::vector<double> va = to_vec(a), vb = to_vec(b);
+        const std::vector<double> c = nogil([&] { return amdkube::mfma_gemm_fp64_host(va, vb, mm, nn, k, dev); });
+        return py::array_t<double>({mm, nn}, c.data());
+      },
+      py::arg("a"), py::arg("b"), py::arg("m"), py::arg("n"), py::arg("k"), py::arg("device") = 0);
+  m.def(
+      "mfma_gemm_int8",
+      [](array_in<int8_t> a, array_in<int8_t> b, int mm, int nn, int k, int dev) {
+        const std::vector<int8_t> va = to_vec(a), vb = to_vec(b);
+        const std::vector<int> c = nogil([&] { return amdkube::mfma_gemm_int8_host(va, vb, mm, nn, k, dev); });
+        return py::array_t<int>({mm, nn}, c.data());
+      },
+      py::arg("a"), py::arg("b"), py::arg("m"), py::arg("n"), py::arg("k"), py::arg("device") = 0);
+  m.def(
+      "mfma_check_wide_tile",
+      [](const std::string& dtype, int block, uint32_t seed, int dev) {
+        const int fmt = amdkube::mfma_check_fmt(dtype);
+        return tile_tuple(nogil([&] { return amdkube::mfma_check_wide_tile_host(fmt, block, seed, dev); }));
       },
       py::arg("dtype"), py::arg("block"), py::arg("seed") = 0x5eedu, py::arg("device") = 0);
   // the per-CU check (kernels/cu_check.h): units is a mask over lds = 1, valu = 2, trans = 4
