@@ -339,6 +339,31 @@ def hbm_copy(words, device: int = 0, grid: int = 0):
     return np.asarray(_need().hbm_copy_words(_np(words, np.uint32).ravel(), device, grid))
 
 
+# ---- xgmi-probe's verifier (kernels/xgmi_verify.h); `grid` as in the hbm_* wrappers above
+def xgmi_fill(count: int, rank: int, seed: int = 0x5EED, device: int = 0, grid: int = 0):
+    """What rank `rank`, in [0, 64), puts into an all-reduce of `count` elements: (rank + 1) + 0.5 * term(seed, e),
+    from the probe's fill kernel, as a float32 array (amdkube.ops.xgmiverify has the arithmetic)."""
+    import numpy as np
+    from . import xgmiverify
+    xgmiverify.check_args(rank=rank, grid=grid)
+    if int(count) < 0:
+        raise ValueError("count must not be negative")
+    return np.asarray(_need().xgmi_fill(int(count), int(rank), int(seed) & 0xFFFFFFFF, device, int(grid)))
+
+
+def xgmi_count_wrong(values, ranks: int, seed: int = 0x5EED, device: int = 0, grid: int = 0) -> dict:
+    """The probe's count kernel over `values` (float32): `wrong`, the elements that are not the sum over
+    `ranks` ranks, in [1, 64], compared with != so that a NaN is wrong, and `records`, at most 16 of them as
+    `index`, `got` and `want` (raw float32 bits)."""
+    import numpy as np
+    from . import xgmiverify
+    xgmiverify.check_args(ranks=ranks, grid=grid)
+    r = dict(_need().xgmi_count_wrong(_np(values, np.float32).ravel(), int(ranks), int(seed) & 0xFFFFFFFF, device, int(grid)))
+    r["wrong"] = int(r["wrong"])
+    r["records"] = [dict(e) for e in r["records"]]
+    return r
+
+
 # ---- hsa-vector-add's kernels (kernels/vadd_kernel.hip) from the code object that program embeds
 VADD_CODE_OBJECT = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "_native", "lib", "vadd_gfx950.co")
 

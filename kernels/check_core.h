@@ -1,5 +1,6 @@
 // Host-side policy shared by the GPU integrity checks (mfma_check.h, cu_check.h) and the burn: how a
-// run is calibrated to its duration, where the self-test flips go, how a comma list is split.
+// run is calibrated to its duration, where the self-test flips go, how a comma list is split; and mix32,
+// the hash that host and device share.
 // Plain C++17 with no HIP include, so native/check_core_selftest.cpp checks it on the CPU, plain and
 // under ASan/UBSan.
 #pragma once
@@ -9,7 +10,30 @@
 #include <string>
 #include <vector>
 
+// for what the host and a kernel both compute: empty without HIP
+#if defined(__HIP__)
+#define AK_HOST_DEVICE __attribute__((host)) __attribute__((device))
+#else
+#define AK_HOST_DEVICE
+#endif
+
 namespace amdkube {
+
+// The project's one integer hash: every pattern, seed and self-test position is made of it, on the device
+// and in the host code that predicts what the device wrote.
+AK_HOST_DEVICE inline __attribute__((always_inline)) uint32_t mix32(uint32_t x) {
+  x ^= x >> 16;
+  x *= 0x7feb352du;
+  x ^= x >> 15;
+  x *= 0x846ca68bu;
+  x ^= x >> 16;
+  return x;
+}
+
+// the checks' hash of (seed, workgroup, index)
+AK_HOST_DEVICE inline __attribute__((always_inline)) uint32_t mix32(uint32_t seed, uint32_t block, uint32_t index) {
+  return mix32(mix32(seed ^ (0x9e3779b9u * (block + 1))) + index);
+}
 
 struct Calibrated {
   int rounds;

@@ -5,7 +5,7 @@
 // device health that comes solely from the plugin (api.proto:97). amdkube replaces that
 // with five CDNA4-native workloads behind the standalone pod binaries (rocm-vector-add,
 // hbm-probe, gpu-burn, mfma-check, cu-check) and the in-process Python extension (_hipops).
-// This header is the base: the first three, and mix32 and the vector types the checks build on.
+// This header is the base: the first three, and the vector types the checks build on (mix32: check_core.h).
 //
 //   vector add   wave64 grid-stride, 16-B (float4) loads, grid sized to the chip
 //   HBM probe    address-hashed write / verify / read / copy over buffers larger than
@@ -25,7 +25,9 @@
 //                transcendental unit on two waves, and the XCD / shader engine / CU it ran on
 //   HBM check    (hbm_check.h, behind hbm-check) a MATS++ march on the pattern below over a region planned by
 //                hbm_plan.h: every bit read in both states, every error with its offset, bits and place
-// The host side is shared: gpu_host.h (AK_HIP, DevInfo, DevBuf, GpuTimer), check_core.h (calibration,
+//   xgmi verify  (xgmi_verify.h, behind xgmi-probe) the fill and count of the all-reduce check, on the
+//                position-hashed values of xgmi_pattern.h
+// The host side is shared: gpu_host.h (AK_HIP, DevInfo, DevBuf, GpuTimer), check_core.h (mix32, calibration,
 // self-test flip positions, list splitting) and vadd_contract.h (the pod workload's contract, which
 // hsa-vector-add shares: flags, inputs, verification, stream_grid, output lines, exit codes); the last
 // two are plain C++, self-tested on the CPU.
@@ -61,19 +63,7 @@ __global__ __launch_bounds__(VADD_WG) void vadd_kernel(const float* __restrict__
     for (size_t i = (n4 << 2) + threadIdx.x; i < n; i += blockDim.x) c[i] = a[i] + b[i];
 }
 
-__device__ __forceinline__ uint32_t mix32(uint32_t x) {
-  x ^= x >> 16;
-  x *= 0x7feb352du;
-  x ^= x >> 15;
-  x *= 0x846ca68bu;
-  x ^= x >> 16;
-  return x;
-}
-
-// the checks' hash of (seed, workgroup, index)
-__device__ __forceinline__ uint32_t mix32(uint32_t seed, uint32_t block, uint32_t index) {
-  return mix32(mix32(seed ^ (0x9e3779b9u * (block + 1))) + index);
-}
+// (mix32, one- and three-argument, for host and device: check_core.h)
 
 // Where a wave runs: the raw HW_ID and XCC_ID words (the field layout and what an MI355X shows in them:
 // cu_check.h) and their decoding into (xcc, se, sh, cu). For the checks that say where an error was seen.

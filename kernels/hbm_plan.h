@@ -15,6 +15,8 @@
 #include <string>
 #include <vector>
 
+#include "check_core.h"
+
 namespace amdkube {
 
 constexpr unsigned long long HBM_SLOT_BYTES = 16;
@@ -86,18 +88,8 @@ inline uint32_t hbm_chunk_of_page(const HbmPlan& p, unsigned long long page) {
 // the first page of a chunk: where the kernel's per-page counters of that chunk start
 inline unsigned long long hbm_first_page(const HbmPlan& p, uint32_t chunk) { return chunk * p.chunk_bytes / HBM_PAGE_BYTES; }
 
-// ---- the seed of one chunk's background in one round: mix32(seed, round, chunk) of gpu_common.h on the
-// host, so two chunks, or two rounds, never expect the same data at the same slot
-inline uint32_t hbm_mix32(uint32_t x) {
-  x ^= x >> 16;
-  x *= 0x7feb352du;
-  x ^= x >> 15;
-  x *= 0x846ca68bu;
-  x ^= x >> 16;
-  return x;
-}
-inline uint32_t hbm_chunk_seed(uint32_t seed, uint32_t round, uint32_t chunk) {
-  return hbm_mix32(hbm_mix32(seed ^ (0x9e3779b9u * (round + 1))) + chunk);
-}
+// ---- the seed of one chunk's background in one round: mix32(seed, round, chunk) of check_core.h, so two
+// chunks, or two rounds, never expect the same data at the same slot
+inline uint32_t hbm_chunk_seed(uint32_t seed, uint32_t round, uint32_t chunk) { return mix32(seed, round, chunk); }
 
 }  // namespace amdkube

@@ -146,7 +146,8 @@ int main() {
 
   // ---- seeds: distinct over rounds and chunks, and the hash itself against values worked by hand
   {
-    CHECK(hbm_mix32(0) == 0 && hbm_mix32(1) == 0x688990c0u);
+    CHECK(mix32(0) == 0 && mix32(1) == 0x688990c0u);
+    CHECK(hbm_chunk_seed(0x5eedu, 2, 5) == mix32(mix32(0x5eedu ^ (0x9e3779b9u * 3u)) + 5u));
     std::set<uint32_t> seen;
     for (uint32_t round = 0; round < 16; ++round)
       for (uint32_t chunk = 0; chunk < 288; ++chunk) seen.insert(hbm_chunk_seed(0x5eedu, round, chunk));

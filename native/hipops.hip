@@ -10,6 +10,7 @@
 #include "../kernels/cu_check.h"
 #include "../kernels/hbm_check.h"
 #include "../kernels/mfma_check_wide.h"
+#include "../kernels/xgmi_verify.h"
 
 namespace py = pybind11;
 
@@ -142,7 +143,7 @@ static py::tuple tile_tuple(const amdkube::MfmaCheckTileOf<V>& t) {
 }
 
 PYBIND11_MODULE(_hipops, m) {
-  m.doc() = "amdkube HIP (gfx950) validation kernels: vector add, HBM probe, HBM check, MFMA burn, MFMA check, CU check";
+  m.doc() = "amdkube HIP (gfx950) validation kernels: vector add, HBM probe, HBM check, MFMA burn, MFMA check, CU check, xgmi verifier";
   m.def("device_count", []() {
     int n = 0;
     AK_HIP(hipGetDeviceCount(&n));
@@ -399,6 +400,33 @@ PYBIND11_MODULE(_hipops, m) {
       },
       py::arg("words"), py::arg("seed"), py::arg("inv"), py::arg("down"), py::arg("write"), py::arg("device") = 0,
       py::arg("grid") = 0);
+  // xgmi-probe's verifier (kernels/xgmi_verify.h): what a rank contributes, and the count over a result
+  m.def(
+      "xgmi_fill",
+      [](size_t count, int rank, uint32_t seed, int dev, int grid) {
+        const std::vector<float> v = nogil([&] { return amdkube::xgmi_fill_host(count, rank, seed, dev, grid); });
+        return py::array_t<float>(v.size(), v.data());
+      },
+      py::arg("count"), py::arg("rank"), py::arg("seed") = 0x5eedu, py::arg("device") = 0, py::arg("grid") = 0);
+  m.def(
+      "xgmi_count_wrong",
+      [](array_in<float> values, int ranks, uint32_t seed, int dev, int grid) {
+        const std::vector<float> v = to_vec(values);
+        const amdkube::XgmiCount r = nogil([&] { return amdkube::xgmi_count_wrong_host(v, ranks, seed, dev, grid); });
+        py::list recs;
+        for (const amdkube::XgmiRecord& e : r.records) {
+          py::dict d;
+          d["index"] = e.index;
+          d["got"] = e.got;
+          d["want"] = e.want;
+          recs.append(d);
+        }
+        py::dict o;
+        o["wrong"] = r.wrong;
+        o["records"] = recs;
+        return o;
+      },
+      py::arg("values"), py::arg("ranks"), py::arg("seed") = 0x5eedu, py::arg("device") = 0, py::arg("grid") = 0);
   m.def(
       "mfma_burn",
       [](double ms, int dev) {
