@@ -176,7 +176,7 @@ def hbm_check_timeout(mib: int) -> float:
 # --ms 200` on every GPU after the probe list and before the HBM march (also when the list is `none`). It is
 # how the FP64 and INT8 matrix paths (fp64, int8: kernels/mfma_check_wide.h) are checked; LIST is any comma
 # list over the names mfma-check --dtype takes.
-MFMA_CHECK_DTYPES = ("bf16", "fp8", "mxfp8", "mxfp4", "fp64", "int8")
+MFMA_CHECK_DTYPES = ("bf16", "fp8", "mxfp8", "mxfp4", "fp64", "int8", "sp-bf16", "sp-int8")
 
 
 def parse_mfma_check_dtype(spec: str) -> str:

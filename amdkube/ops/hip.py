@@ -180,9 +180,42 @@ def mfma_gemm_int8(a, b, device: int = 0):
     return torch.from_numpy(np.asarray(c).copy())
 
 
+SPARSE_DTYPES = ("sp-bf16", "sp-int8")    # the 2:4 sparse matrix-core paths (kernels/mfma_check_sparse.h)
+
+
+def mfma_gemm_sparse(a, b, dtype: str = "sp-bf16", device: int = 0):
+    """C = A @ B with the LDS-staged 64×64 tile kernel on v_smfmac_f32_32x32x32_bf16 (`sp-bf16`) or
+    v_smfmac_i32_32x32x64_i8 (`sp-int8`): A is a dense M×K matrix that is 2:4 sparse (at most two
+    non-zeros in every aligned group of four k, else a ValueError; amdkube.ops.sparse24.prune makes one)
+    and goes to the kernel compressed by sparse24.compress, B is K×N. M and N multiples of 64, K a
+    multiple of 32 (`sp-bf16`) or 64 (`sp-int8`). `sp-bf16` rounds the inputs to bf16 as the matrix core
+    sees them and gives an fp32 tensor; `sp-int8` takes integers in [-128, 127] of any dtype (anything
+    else is a ValueError) and gives an int32 tensor."""
+    import numpy as np
+    import torch
+    from . import sparse24
+    if dtype not in SPARSE_DTYPES:
+        raise ValueError(f"unknown sparse dtype {dtype!r}: expected {' or '.join(SPARSE_DTYPES)}")
+    if dtype == "sp-bf16":
+        a, b = (torch.as_tensor(x).to(torch.bfloat16).to(torch.float32) for x in (a, b))
+        elems = lambda x: (np.ascontiguousarray(x, np.float32).view(np.uint32) >> 16).astype(np.uint16)   # noqa: E731
+    else:
+        elems = lambda x: x.astype(np.int8)   # noqa: E731
+    a, b = _np(a, None), _np(b, None)
+    if dtype == "sp-int8":
+        for x in (a, b):
+            if x.size and (not np.array_equal(x, np.rint(x)) or x.min() < -128 or x.max() > 127):
+                raise ValueError("int8 operands must be integers in [-128, 127]")
+    m, n, k = _gemm_wide_shapes(a, b, 32 if dtype == "sp-bf16" else 64)
+    values, meta = sparse24.compress(a)
+    c = _need().mfma_gemm_sparse(dtype, elems(values).view(np.uint8).ravel(), meta.ravel(),
+                                 elems(b).view(np.uint8).ravel(), m, n, k, device)
+    return torch.from_numpy(np.asarray(c).copy())
+
+
 def _check_dtype(dtype):
-    if dtype != "bf16" and dtype not in LP_DTYPES and dtype not in WIDE_DTYPES:
-        raise ValueError(f"unknown dtype {dtype!r}: expected bf16, {', '.join(LP_DTYPES + WIDE_DTYPES)}")
+    if dtype != "bf16" and dtype not in LP_DTYPES + WIDE_DTYPES + SPARSE_DTYPES:
+        raise ValueError(f"unknown dtype {dtype!r}: expected bf16, {', '.join(LP_DTYPES + WIDE_DTYPES + SPARSE_DTYPES)}")
 
 
 def mfma_check(rounds: int | None = None, ms: float = 50.0, device: int = 0, seed: int = 0x5EED,
@@ -191,9 +224,11 @@ def mfma_check(rounds: int | None = None, ms: float = 50.0, device: int = 0, see
     compared with exact integer arithmetic in round 0 and bitwise with round 0 afterwards. `rounds`
     runs exactly that many, otherwise the run is calibrated to ~`ms`. `selftest_flips` perturbs
     that many compared values, which the check must then report. `dtype` picks the matrix-core path:
-    bf16, fp8, mxfp8, mxfp4, fp64 or int8; the result carries `dtype` and `tflops` (bf16 also
-    `bf16_tflops`). For int8 `tflops` counts integer operations, 1e12 a second, and for fp64 a record's
-    `got` and `want` are the 32-bit half of the value that differs, the low one if both do."""
+    bf16, fp8, mxfp8, mxfp4, fp64, int8, sp-bf16 or sp-int8; the result carries `dtype` and `tflops` (bf16
+    also `bf16_tflops`). For int8 `tflops` counts integer operations, 1e12 a second, and for fp64 a record's
+    `got` and `want` are the 32-bit half of the value that differs, the low one if both do. For the 2:4
+    sparse dtypes `k` is the dense K and `tflops` counts the dense-equivalent 2·64·64·K per round and
+    workgroup, the way sparse peaks are quoted: the matrix core does half of those multiply-adds."""
     _check_dtype(dtype)
     if rounds is not None and rounds < 1:
         raise ValueError("rounds must be at least 1")
@@ -209,7 +244,8 @@ def mfma_check(rounds: int | None = None, ms: float = 50.0, device: int = 0, see
 def mfma_check_tile(block: int, seed: int = 0x5EED, device: int = 0, dtype: str = "bf16"):
     """(A, B, C) of one workgroup of the check: its hashed 64×K and K×64 operands (decoded, with the
     block scales applied for the MX dtypes) and the 64×64 round-0 MFMA result, as fp32 tensors, or
-    as float64 tensors for fp64 and int8, which holds every value of either exactly."""
+    as float64 tensors for fp64, int8 and the sparse dtypes, which holds every value of those exactly.
+    A sparse dtype's A comes expanded to dense, so A @ B == C holds as for the others."""
     import numpy as np
     import torch
     _check_dtype(dtype)
@@ -217,7 +253,7 @@ def mfma_check_tile(block: int, seed: int = 0x5EED, device: int = 0, dtype: str 
     if dtype == "bf16":
         t = ext.mfma_check_tile(block, seed, device)
     else:
-        t = (ext.mfma_check_wide_tile if dtype in WIDE_DTYPES else ext.mfma_check_lp_tile)(dtype, block, seed, device)
+        t = (ext.mfma_check_wide_tile if dtype in WIDE_DTYPES + SPARSE_DTYPES else ext.mfma_check_lp_tile)(dtype, block, seed, device)
     return tuple(torch.from_numpy(np.asarray(x).copy()) for x in t)
 
 

@@ -19,7 +19,8 @@
 //   MFMA check   (mfma_check.h) LDS-staged 64x64 bf16 tiles whose every result is compared:
 //                round 0 with exact int32 arithmetic, later rounds bitwise with round 0;
 //                (mfma_check_lp.h) the same on the FP8 MFMA and the block-scaled MXFP8 / MXFP4 forms;
-//                (mfma_check_wide.h) the same on the FP64 and INT8 MFMAs, with 64-bit and int32 accumulators
+//                (mfma_check_wide.h) the same on the FP64 and INT8 MFMAs, with 64-bit and int32 accumulators;
+//                (mfma_check_sparse.h) the same on the 2:4 sparse bf16 and int8 SMFMACs, A compressed with index words
 //   CU check     (cu_check.h) one workgroup per CU with all 160 KiB of LDS: a march over the LDS, the
 //                same multiply-adds on the fp32, packed-fp32, fp64 and integer pipes, the
 //                transcendental unit on two waves, and the XCD / shader engine / CU it ran on

@@ -7,13 +7,15 @@
 // values to prove the checker reports them. Prints one JSON line; exit 1 on any mismatch.
 // --dtype takes a comma list over bf16, fp8, mxfp8 and mxfp4 (the FP8 MFMA and the block-scaled
 // e4m3 / e2m1 forms, kernels/mfma_check_lp.h), fp64 and int8 (the FP64 and the integer matrix paths,
-// kernels/mfma_check_wide.h; "tflops" counts integer operations for int8): one JSON line per dtype in the order given, each
+// kernels/mfma_check_wide.h; "tflops" counts integer operations for int8), sp-bf16 and sp-int8 (the 2:4 sparse
+// v_smfmac paths, kernels/mfma_check_sparse.h; "tflops" counts the dense-equivalent 2*64*64*K per round and
+// workgroup, the way sparse peaks are quoted): one JSON line per dtype in the order given, each
 // with "dtype" and "tflops", stopping after the first dtype with mismatches; the other flags apply
 // to each dtype. Exit 2 on an unknown dtype, 4 on a runtime error.
 #include <cstdlib>
 #include <cstring>
 
-#include "mfma_check_wide.h"
+#include "mfma_check_sparse.h"
 
 static void print_errors(const amdkube::MfmaCheckResult& r) {
   std::printf("\"errors\":%llu,\"first_errors\":[", r.errors);
@@ -44,7 +46,7 @@ int main(int argc, char** argv) {
     try {
       fmts.push_back(amdkube::mfma_check_fmt(name, amdkube::MFMA_BF16));
     } catch (const std::invalid_argument&) {
-      std::fprintf(stderr, "mfma-check: unknown dtype '%s': expected a comma list over bf16, fp8, mxfp8, mxfp4, fp64, int8\n",
+      std::fprintf(stderr, "mfma-check: unknown dtype '%s': expected a comma list over bf16, fp8, mxfp8, mxfp4, fp64, int8, sp-bf16, sp-int8\n",
                    name.c_str());
       return 2;
     }

@@ -26,8 +26,11 @@
 namespace amdkube {
 
 // MFMA_BF16 is the check of mfma_check.h, so that one list of formats serves mfma-check; it has no GEMM here
-// the two after it are the formats of mfma_check_wide.h, which no table or default of this header reaches
-enum MfmaLpFmt { MFMA_LP_FP8 = 0, MFMA_LP_MXFP8 = 1, MFMA_LP_MXFP4 = 2, MFMA_BF16 = 3, MFMA_WIDE_FP64 = 4, MFMA_WIDE_INT8 = 5 };
+// the four after it are the formats of mfma_check_wide.h and mfma_check_sparse.h, which no table or default of this header reaches
+enum MfmaLpFmt {
+  MFMA_LP_FP8 = 0, MFMA_LP_MXFP8 = 1, MFMA_LP_MXFP4 = 2, MFMA_BF16 = 3, MFMA_WIDE_FP64 = 4, MFMA_WIDE_INT8 = 5,
+  MFMA_SPARSE_BF16 = 6, MFMA_SPARSE_INT8 = 7
+};
 
 typedef int lp_v4i __attribute__((ext_vector_type(4)));
 typedef int lp_v8i __attribute__((ext_vector_type(8)));

@@ -367,33 +367,7 @@ inline void mfma_check_wide_launch(const MfmaCheckRun& run, int rounds, int flip
 
 inline bool mfma_fmt_is_wide(int fmt) { return fmt == MFMA_WIDE_FP64 || fmt == MFMA_WIDE_INT8; }
 
-// mfma_fmt_ops over every format of the check: the wide ones have no GEMM in that table
-inline const MfmaFmtOps& mfma_check_fmt_ops(int fmt) {
-  static const MfmaFmtOps wide[] = {{"fp64", mfma_check_wide_launch<MfmaWideFp64>, MfmaWideFp64::CHECK_K, nullptr},
-                                    {"int8", mfma_check_wide_launch<MfmaWideInt8>, MfmaWideInt8::CHECK_K, nullptr}};
-  return mfma_fmt_is_wide(fmt) ? wide[fmt - MFMA_WIDE_FP64] : mfma_fmt_ops(fmt);
-}
-
-// fp64 or int8, else what mfma_lp_fmt(name, last) says
-inline int mfma_check_fmt(const std::string& name, int last = MFMA_LP_MXFP4) {
-  for (int f = MFMA_WIDE_FP64; f <= MFMA_WIDE_INT8; ++f)
-    if (name == mfma_check_fmt_ops(f).name) return f;
-  return mfma_lp_fmt(name, last);
-}
-
-// run_mfma_check_lp over every format of the check
-inline MfmaCheckResult run_mfma_check_fmt(int fmt, int rounds, double target_ms, int dev, uint32_t seed = 0x5eedu,
-                                          int flips = 0) {
-  const MfmaFmtOps& ops = mfma_check_fmt_ops(fmt);
-  return mfma_check_drive(ops.check, ops.check_k, rounds, target_ms, dev, seed, flips);
-}
-
-// A, B and the round-0 C of one workgroup of a wide check, as doubles
-inline MfmaCheckTileOf<double> mfma_check_wide_tile_host(int fmt, int block, uint32_t seed, int dev) {
-  if (!mfma_fmt_is_wide(fmt)) throw std::invalid_argument("not a wide format");
-  const MfmaFmtOps& ops = mfma_check_fmt_ops(fmt);
-  return mfma_check_fetch_tile<double>(ops.check, ops.check_k, block, seed, dev);
-}
+// (the table over every format of the check, mfma_check_fmt_ops, and what runs on it: mfma_check_sparse.h)
 
 inline size_t mfma_wide_tiles(int m, int n, int k, int kstep) {
   if (m <= 0 || n <= 0 || m % MFMA_TILE || n % MFMA_TILE)

@@ -151,7 +151,7 @@ def targets(sanitize=False, cpu_only=False):
         base = [n("kernels/gpu_common.h"), n("kernels/gpu_host.h"), n("kernels/check_core.h"), n("kernels/vadd_contract.h")]
         chk = [n("kernels/mfma_check.h"), *base]
         lp = [n("kernels/mfma_check_lp.h"), *chk]
-        wide = [n("kernels/mfma_check_wide.h"), *lp]
+        wide = [n("kernels/mfma_check_sparse.h"), n("kernels/mfma_check_wide.h"), *lp]
         cu = [n("kernels/cu_check.h"), *base]
         hbm = [n("kernels/hbm_check.h"), n("kernels/hbm_plan.h"), *base]
         xgmi = [n("kernels/xgmi_verify.h"), n("kernels/xgmi_pattern.h"), *base]

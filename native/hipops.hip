@@ -9,7 +9,7 @@
 
 #include "../kernels/cu_check.h"
 #include "../kernels/hbm_check.h"
-#include "../kernels/mfma_check_wide.h"
+#include "../kernels/mfma_check_sparse.h"
 #include "../kernels/xgmi_verify.h"
 
 namespace py = pybind11;
@@ -276,7 +276,7 @@ PYBIND11_MODULE(_hipops, m) {
       },
       py::arg("block"), py::arg("seed") = 0x5eedu, py::arg("device") = 0);
   // the low-precision matrix-core paths (kernels/mfma_check_lp.h): dtype is fp8, mxfp8 or mxfp4;
-  // mfma_check_lp also takes the wide dtypes fp64 and int8 (kernels/mfma_check_wide.h)
+  // mfma_check_lp also takes the wide dtypes fp64 and int8 (kernels/mfma_check_wide.h) and the sparse ones
   m.def(
       "mfma_gemm_lp",
       [](const std::string& dtype, bytes_in a_codes, bytes_in b_codes, bytes_in a_scales, bytes_in b_scales, int mm, int nn,
@@ -329,6 +329,20 @@ PYBIND11_MODULE(_hipops, m) {
         return tile_tuple(nogil([&] { return amdkube::mfma_check_wide_tile_host(fmt, block, seed, dev); }));
       },
       py::arg("dtype"), py::arg("block"), py::arg("seed") = 0x5eedu, py::arg("device") = 0);
+  // the 2:4 sparse matrix-core paths (kernels/mfma_check_sparse.h): dtype is sp-bf16 or sp-int8, values and b
+  // are the bytes of bf16 or int8 elements; mfma_check_lp and mfma_check_wide_tile take both dtypes too
+  m.def(
+      "mfma_gemm_sparse",
+      [](const std::string& dtype, bytes_in values, array_in<uint32_t> meta, bytes_in b, int mm, int nn, int k, int dev) {
+        const int fmt = amdkube::mfma_check_fmt(dtype);
+        const std::vector<uint8_t> vv = to_vec(values), vb = to_vec(b);
+        const std::vector<uint32_t> vm = to_vec(meta);
+        const std::vector<uint32_t> c = nogil([&] { return amdkube::mfma_gemm_sparse_host(fmt, vv, vm, vb, mm, nn, k, dev); });
+        if (fmt == amdkube::MFMA_SPARSE_INT8) return py::array(py::array_t<int>({mm, nn}, reinterpret_cast<const int*>(c.data())));
+        return py::array(py::array_t<float>({mm, nn}, reinterpret_cast<const float*>(c.data())));
+      },
+      py::arg("dtype"), py::arg("values"), py::arg("meta"), py::arg("b"), py::arg("m"), py::arg("n"), py::arg("k"),
+      py::arg("device") = 0);
   // the per-CU check (kernels/cu_check.h): units is a mask over lds = 1, valu = 2, trans = 4
   m.def(
       "cu_check",
