@@ -918,6 +918,18 @@ def device_plugin_parser():
                     help="also run the matrix-core check on a comma list of dtypes (mfma-check --dtype LIST --ms 200; "
                          "fp64,int8 covers the FP64 and the integer matrix paths, which no --health-probe entry does) after "
                          "the --health-probe list and before --hbm-check-mib, or alone with none; empty: off")
+    def check_ms(text):
+        try:
+            n = int(text)
+        except ValueError:
+            raise argparse.ArgumentTypeError(f"not a number of milliseconds: {text!r}")
+        if n < 0:
+            raise argparse.ArgumentTypeError("must not be negative (0: off)")
+        return n
+    ap.add_argument("--atomic-check-ms", default=0, type=check_ms, metavar="N",
+                    help="also run the atomic-unit check for N ms on every GPU (atomic-check --ms N: a scatter-reduce "
+                         "through the global and LDS atomic ALUs, every slot recomputed and compared) after the "
+                         "--health-probe list and --mfma-check-dtype and before --hbm-check-mib, or alone with none; 0: off")
     ap.add_argument("--max-gpus", type=int, default=None, help="advertise only the first N physical GPUs")
     ap.add_argument("--resource-naming", default="single", choices=("single", "mixed"),
                     help="partitioned GPUs: single=amd.com/gpu for all, mixed=amd.com/<cpx>_<nps> per partition type")
@@ -951,7 +963,7 @@ def device_plugin(argv):
         plugins = make_plugins(backend, a.resource_naming, a.resource_name, plugins_dir=a.plugins_dir,
                                health_interval=a.health_interval, health_probe=a.health_probe,
                                health_state=state or None, hbm_check_mib=a.hbm_check_mib,
-                               mfma_check_dtype=a.mfma_check_dtype)
+                               mfma_check_dtype=a.mfma_check_dtype, atomic_check_ms=a.atomic_check_ms)
         for p in plugins:
             await p.start()
             if a.register_v1beta1:

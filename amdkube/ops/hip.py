@@ -299,6 +299,60 @@ def cu_check_dump(block: int, seed: int = 0x5EED, device: int = 0) -> dict:
     return d
 
 
+def atomic_check(rounds: int | None = None, ms: float = 50.0, device: int = 0, seed: int = 0x5EED, selftest_flips: int = 0,
+                 units="int,fp,ret,lds", contention=None, blocks: int | None = None) -> dict:
+    """The atomic-unit integrity check (atomic-check in process, kernels/atomic_check.h): per round and per
+    contention level (lanes per slot, powers of two; default 1, 64, 4096) a scatter through the global
+    atomic ALUs (`int`, `fp`, and `ret`: a ticket counter and a compare-and-swap loop) and the LDS atomic
+    ALU of every CU (`lds`), whose result does not depend on the arrival order, then a verify kernel that
+    recomputes every slot without atomics. `rounds` runs exactly that many, otherwise the run is calibrated
+    to ~`ms`. `selftest_flips` (at most 64) flips one bit of that many table slots of the first level
+    between scatter and verify (`selftest_positions`: `op`, `slot`, `contention`), which the check must
+    then report. The result carries `checked` (slot-ops compared), `atomics_per_s`, `errors`,
+    `errors_by_unit` and `first_errors`: `unit`, `op`, `slot`, `round`, `contention`, `offset`, `got`,
+    `want`, and for `lds` the `xcc`, `se`, `sh`, `cu` of the workgroup."""
+    from . import atomiccheck
+    mask = atomiccheck.units_mask(units)
+    blocks = atomiccheck.DEFAULT_BLOCKS if blocks is None else int(blocks)
+    if blocks < 1 or blocks & (blocks - 1) or blocks > atomiccheck.MAX_BLOCKS:
+        raise ValueError(f"blocks must be a power of two in [1, {atomiccheck.MAX_BLOCKS}]")
+    levels = atomiccheck.check_contention(atomiccheck.DEFAULT_CONTENTION if contention is None else contention, blocks)
+    if rounds is not None and rounds < 1:
+        raise ValueError("rounds must be at least 1")
+    if not 0 <= int(selftest_flips) <= atomiccheck.MAX_FLIPS:
+        raise ValueError(f"selftest_flips must be in [0, {atomiccheck.MAX_FLIPS}]")
+    r = dict(_need().atomic_check(int(rounds or 0), float(ms), device, seed, int(selftest_flips), mask, levels, blocks))
+    for k in ("first_errors", "selftest_positions"):
+        r[k] = [dict(e) for e in r[k]]
+    r["errors_by_unit"] = dict(r["errors_by_unit"])
+    r["units"], r["contention"] = list(r["units"]), list(r["contention"])
+    return r
+
+
+def atomic_check_tables(contention: int, blocks: int, seed: int = 0x5EED, round: int = 0, units="int,fp,ret,lds",
+                        device: int = 0) -> dict:
+    """What init and one scatter launch of round `round` leave behind, as numpy arrays: every global table
+    under its op name (S = 256 blocks / contention slots; dtypes as amdkube.ops.atomiccheck.VIEWS reads them,
+    the packed ops as uint32 bits), `order` (shape (S, n), as the lanes wrote it), and `lds`: workgroup 0's
+    LDS tables by op name, taken before its in-kernel verification re-initialises them. For tests."""
+    import numpy as np
+    from . import atomiccheck
+    mask = atomiccheck.units_mask(units)
+    if blocks < 1 or blocks & (blocks - 1) or blocks > atomiccheck.MAX_BLOCKS:
+        raise ValueError(f"blocks must be a power of two in [1, {atomiccheck.MAX_BLOCKS}]")
+    c, = atomiccheck.check_contention([contention], blocks)
+    d = dict(_need().atomic_check_tables(c, int(blocks), seed, int(round), mask, device))
+
+    def typed(tables):
+        return {op: np.asarray(v).copy().view(atomiccheck.VIEWS.get(op, v.dtype)) for op, v in dict(tables).items()}
+    out = typed({k: v for k, v in d.items() if k not in ("order", "lds")})
+    if "order" in d:
+        out["order"] = np.asarray(d["order"]).copy().reshape(blocks * atomiccheck.WG // c, c * atomiccheck.STEPS)
+    if "lds" in d:
+        out["lds"] = typed(d["lds"])
+    return out
+
+
 def hbm_check(mib: int | None = None, rounds: int = 1, seed: int = 0x5EED, selftest_flips: int = 0, chunk_mib: int = 1024,
               hold_ms: int = 0, device: int = 0, free_fraction: float | None = None) -> dict:
     """The HBM integrity check (hbm-check in process, kernels/hbm_check.h): a march over `mib` MiB

@@ -26,6 +26,8 @@
 //                transcendental unit on two waves, and the XCD / shader engine / CU it ran on
 //   HBM check    (hbm_check.h, behind hbm-check) a MATS++ march on the pattern below over a region planned by
 //                hbm_plan.h: every bit read in both states, every error with its offset, bits and place
+//   Atomic check (atomic_check.h, behind atomic-check) an order-independent scatter-reduce through the global and
+//                LDS atomic ALUs on the slot map and operands of atomic_plan.h, every slot recomputed without atomics
 //   xgmi verify  (xgmi_verify.h, behind xgmi-probe) the fill and count of the all-reduce check, on the
 //                position-hashed values of xgmi_pattern.h
 // The host side is shared: gpu_host.h (AK_HIP, DevInfo, DevBuf, GpuTimer), check_core.h (mix32, calibration,

@@ -7,6 +7,7 @@
 #include <pybind11/pybind11.h>
 #include <pybind11/stl.h>
 
+#include "../kernels/atomic_check.h"
 #include "../kernels/cu_check.h"
 #include "../kernels/hbm_check.h"
 #include "../kernels/mfma_check_sparse.h"
@@ -371,6 +372,81 @@ PYBIND11_MODULE(_hipops, m) {
         return o;
       },
       py::arg("block"), py::arg("seed") = 0x5eedu, py::arg("device") = 0);
+  // the atomic-unit check (kernels/atomic_check.h): units is a mask over int = 1, fp = 2, ret = 4, lds = 8;
+  // an empty contention list takes the default levels
+  m.def(
+      "atomic_check",
+      [](int rounds, double ms, int dev, uint32_t seed, int flips, int units, std::vector<uint32_t> contention, int blocks) {
+        const amdkube::AtomicCheckResult r =
+            nogil([&] { return amdkube::run_atomic_check(rounds, ms, dev, seed, flips, units, contention, blocks); });
+        py::dict o, by_unit;
+        py::list units_l, recs, flipped;
+        for (int u = 0; u < 4; ++u) {
+          if (r.units & (1 << u)) units_l.append(amdkube::ATOMIC_UNIT_NAMES[u]);
+          by_unit[amdkube::ATOMIC_UNIT_NAMES[u]] = r.errors_by_unit[u];
+        }
+        for (const amdkube::AtomicFlip& f : r.flipped) {
+          py::dict d;
+          d["op"] = amdkube::ATOMIC_OP_NAMES[f.op];
+          d["slot"] = f.slot;
+          d["contention"] = f.contention;
+          flipped.append(d);
+        }
+        for (const amdkube::AtomicRecord& e : r.first_errors) {
+          py::dict d = e.unit == 3 ? cu_location(amdkube::cu_decode_location(e.hw_id, e.xcc_id)) : py::dict();
+          d["unit"] = amdkube::ATOMIC_UNIT_NAMES[e.unit < 4 ? e.unit : 0];
+          d["op"] = amdkube::ATOMIC_OP_NAMES[e.op < amdkube::AOP_COUNT ? e.op : 0];
+          d["slot"] = e.slot;
+          d["round"] = e.round;
+          d["contention"] = e.contention;
+          d["offset"] = e.offset;
+          d["got"] = static_cast<unsigned long long>(e.got_hi) << 32 | e.got_lo;
+          d["want"] = static_cast<unsigned long long>(e.want_hi) << 32 | e.want_lo;
+          recs.append(d);
+        }
+        o["ok"] = r.errors == 0;
+        o["errors"] = r.errors;
+        o["errors_by_unit"] = by_unit;
+        o["units"] = units_l;
+        o["contention"] = r.contention;
+        o["blocks"] = r.blocks;
+        o["rounds"] = r.rounds;
+        o["ms"] = r.ms;
+        o["checked"] = r.checked;
+        o["atomics_per_s"] = r.atomics_per_s;
+        o["selftest_positions"] = flipped;
+        o["first_errors"] = recs;
+        return o;
+      },
+      py::arg("rounds") = 0, py::arg("ms") = 50.0, py::arg("device") = 0, py::arg("seed") = 0x5eedu, py::arg("selftest_flips") = 0,
+      py::arg("units") = 15, py::arg("contention") = std::vector<uint32_t>(), py::arg("blocks") = amdkube::ATOMIC_DEFAULT_BLOCKS);
+  m.def(
+      "atomic_check_tables",
+      [](uint32_t contention, int blocks, uint32_t seed, uint32_t round, int units, int dev) {
+        const amdkube::AtomicTables t =
+            nogil([&] { return amdkube::atomic_check_tables_host(contention, blocks, seed, round, units, dev); });
+        // 64-bit ops as uint64, the others as uint32: the bits, which the caller views as the op's type
+        auto arrays = [](const std::vector<std::vector<unsigned long long>>& tables, auto&& has) {
+          py::dict d;
+          for (int op = 0; op < amdkube::AOP_COUNT; ++op) {
+            if (!has(op)) continue;
+            const std::vector<unsigned long long>& v = tables[op];
+            if (amdkube::atomic_op_is64(op)) {
+              d[amdkube::ATOMIC_OP_NAMES[op]] = py::array_t<uint64_t>(v.size(), reinterpret_cast<const uint64_t*>(v.data()));
+            } else {
+              const std::vector<uint32_t> w(v.begin(), v.end());
+              d[amdkube::ATOMIC_OP_NAMES[op]] = py::array_t<uint32_t>(w.size(), w.data());
+            }
+          }
+          return d;
+        };
+        py::dict o = arrays(t.table, [&](int op) { return amdkube::atomic_op_enabled(op, units, contention); });
+        if (units & amdkube::ATOMIC_UNIT_RET) o["order"] = py::array_t<uint32_t>(t.order.size(), t.order.data());
+        if (units & amdkube::ATOMIC_UNIT_LDS) o["lds"] = arrays(t.lds, [](int op) { return amdkube::atomic_op_in_lds(op); });
+        return o;
+      },
+      py::arg("contention"), py::arg("blocks"), py::arg("seed") = 0x5eedu, py::arg("round") = 0, py::arg("units") = 15,
+      py::arg("device") = 0);
   // the HBM march (kernels/hbm_check.h): mib == 0 and free_fraction == 0 mean "not given"
   m.def(
       "hbm_check",
