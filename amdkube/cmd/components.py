@@ -930,6 +930,11 @@ def device_plugin_parser():
                     help="also run the atomic-unit check for N ms on every GPU (atomic-check --ms N: a scatter-reduce "
                          "through the global and LDS atomic ALUs, every slot recomputed and compared) after the "
                          "--health-probe list and --mfma-check-dtype and before --hbm-check-mib, or alone with none; 0: off")
+    ap.add_argument("--lane-check-ms", default=0, type=check_ms, metavar="N",
+                    help="also run the lane check for N ms on every GPU (lane-check --ms N: every DPP control, the lane "
+                         "swaps, ds_bpermute / ds_permute / ds_swizzle, the transposing LDS reads and the direct "
+                         "global-to-LDS loads, every result compared) after --atomic-check-ms and before --hbm-check-mib, "
+                         "or alone with none; 0: off")
     ap.add_argument("--max-gpus", type=int, default=None, help="advertise only the first N physical GPUs")
     ap.add_argument("--resource-naming", default="single", choices=("single", "mixed"),
                     help="partitioned GPUs: single=amd.com/gpu for all, mixed=amd.com/<cpx>_<nps> per partition type")
@@ -963,7 +968,7 @@ def device_plugin(argv):
         plugins = make_plugins(backend, a.resource_naming, a.resource_name, plugins_dir=a.plugins_dir,
                                health_interval=a.health_interval, health_probe=a.health_probe,
                                health_state=state or None, hbm_check_mib=a.hbm_check_mib,
-                               mfma_check_dtype=a.mfma_check_dtype, atomic_check_ms=a.atomic_check_ms)
+                               mfma_check_dtype=a.mfma_check_dtype, atomic_check_ms=a.atomic_check_ms, lane_check_ms=a.lane_check_ms)
         for p in plugins:
             await p.start()
             if a.register_v1beta1:

@@ -185,6 +185,13 @@ MFMA_CHECK_DTYPES = ("bf16", "fp8", "mxfp8", "mxfp4", "fp64", "int8", "sp-bf16",
 ATOMIC_CHECK_TIMEOUT_S = 60
 
 
+# Nor is the lane check: `--lane-check-ms N` runs `lane-check --ms N` on every GPU after the atomic-unit check and
+# before the HBM march (also when the list is `none`): the DPP network, the lane swaps, the LDS crossbar as a
+# permute unit, the transposing LDS reads and the direct global-to-LDS loads of every CU (kernels/lane_check.h).
+# The time limit is that of atomic-check, a program of the same shape.
+LANE_CHECK_TIMEOUT_S = 60
+
+
 def parse_mfma_check_dtype(spec: str) -> str:
     """`` (off), or a comma list over MFMA_CHECK_DTYPES → the list as mfma-check --dtype takes it."""
     if not str(spec):
@@ -215,8 +222,11 @@ class AMDGPUPlugin(DevicePluginServer):
                  health_interval: float = 10.0, health_probe: str = "none", dev_root: str = "/dev",
                  ecc_threshold: int = 0, expose_card: bool = True, init_timeout: int = 10,
                  devices: list[dict] | None = None, health_state: str | None = None, hbm_check_mib: int = 0,
-                 mfma_check_dtype: str = "", atomic_check_ms: int = 0):
+                 mfma_check_dtype: str = "", atomic_check_ms: int = 0, lane_check_ms: int = 0):
         super().__init__(resource_name, plugins_dir, init_timeout)
+        if lane_check_ms < 0:
+            raise ValueError("lane_check_ms must not be negative (0: no lane check)")
+        self.lane_check_ms = int(lane_check_ms)
         if atomic_check_ms < 0:
             raise ValueError("atomic_check_ms must not be negative (0: no atomic-unit check)")
         self.atomic_check_ms = int(atomic_check_ms)
@@ -258,7 +268,7 @@ class AMDGPUPlugin(DevicePluginServer):
     async def start(self):
         for g in self.gpus:             # the RAS baseline new faults are judged against
             self.monitor.snapshot(g["index"])
-        if self.probes or self.hbm_check_mib or self.mfma_check_dtype or self.atomic_check_ms:
+        if self.probes or self.hbm_check_mib or self.mfma_check_dtype or self.atomic_check_ms or self.lane_check_ms:
             await self._probe_all()
         self._check_health(push=False)
         await super().start()
@@ -331,7 +341,7 @@ class AMDGPUPlugin(DevicePluginServer):
 
     async def _probe_all(self):
         """Run the configured on-device probes (HBM pattern, matrix-core checks, per-CU check, then the
-        matrix-core check of mfma_check_dtype, the atomic-unit check of atomic_check_ms and the HBM march of hbm_check_mib, where set) on each GPU (subprocess → isolated HIP context); the first failure
+        matrix-core check of mfma_check_dtype, the atomic-unit check of atomic_check_ms, the lane check of lane_check_ms and the HBM march of hbm_check_mib, where set) on each GPU (subprocess → isolated HIP context); the first failure
         takes the GPU out of service and ends its chain."""
         known = all_health_probes()
         runs = [(*known[probe], 60) for probe in self.probes]
@@ -339,6 +349,8 @@ class AMDGPUPlugin(DevicePluginServer):
             runs.append(("mfma-check", ["--dtype", self.mfma_check_dtype, "--ms", "200"], 60))
         if self.atomic_check_ms:
             runs.append(("atomic-check", ["--ms", str(self.atomic_check_ms)], ATOMIC_CHECK_TIMEOUT_S))
+        if self.lane_check_ms:
+            runs.append(("lane-check", ["--ms", str(self.lane_check_ms)], LANE_CHECK_TIMEOUT_S))
         if self.hbm_check_mib:
             runs.append(("hbm-check", ["--mib", str(self.hbm_check_mib)], hbm_check_timeout(self.hbm_check_mib)))
         for g in self.gpus:

@@ -471,3 +471,43 @@ def hsa_copy_array(src, groups: int, device: int = 0):
     """`src` through `amdkube_copy` on `groups` workgroups; float32 numpy in and out, bit for bit."""
     import numpy as np
     return np.asarray(_need().hsa_copy_array(VADD_CODE_OBJECT, _np(src, np.float32).ravel(), groups, device))
+
+
+def lane_check(rounds: int | None = None, ms: float = 50.0, device: int = 0, seed: int = 0x5EED, selftest_flips: int = 0,
+               units="dpp,perm,tr,dma") -> dict:
+    """The lane check (lane-check in process, kernels/lane_check.h): every workgroup owns a whole CU's LDS and,
+    round after round, runs every DPP control, the lane swaps and v_readlane (`dpp`), ds_bpermute, ds_permute and
+    ds_swizzle (`perm`), the four transposing LDS reads (`tr`) and a sweep of its LDS by the direct global-to-LDS
+    loads in all three widths (`dma`), each result compared with the value worked out from the lane id.
+    `rounds` runs exactly that many, otherwise the run is calibrated to ~`ms`. `selftest_flips` flips one bit of
+    that many compared values, which the check must then report. The result carries `xlane_gops`, `tr_gbps`,
+    `dma_gbps`, the coverage (`cus`, `cus_covered`, `simds`, `simds_covered`, `xccs`, and `block_loc`: per
+    workgroup of the timed launch the raw HW_ID of its 16 waves, then XCC_ID), `errors_by_unit`, `bad_cus` and
+    records with `unit`, `block`, `xcc`, `se`, `sh`, `cu`, `simd`, `round`, `op`, `lane`, `got` and `want`.
+    While SIMDs are missing, up to 3 further launches of one round are added (`launches`)."""
+    from . import lanecheck
+    mask = lanecheck.units_mask(units)
+    if rounds is not None and rounds < 1:
+        raise ValueError("rounds must be at least 1")
+    if not 0 <= int(selftest_flips) <= lanecheck.MAX_FLIPS:
+        raise ValueError(f"selftest_flips must be in [0, {lanecheck.MAX_FLIPS}]")
+    r = dict(_need().lane_check(int(rounds or 0), float(ms), device, seed, int(selftest_flips), mask))
+    for k in ("first_errors", "bad_cus"):
+        r[k] = [dict(e) for e in r[k]]
+    r["errors_by_unit"] = dict(r["errors_by_unit"])
+    r["units"] = list(r["units"])
+    return r
+
+
+def lane_check_dump(block: int, seed: int = 0x5EED, device: int = 0) -> dict:
+    """What workgroup `block` of a one-round check computed, as numpy arrays: the result tables `dpp` [1024, 45]
+    and `perm` [1024, 13], `tr` [1024, 9] (the registers of the four transposing reads), `dma` (the 40,960 LDS
+    words after the sweep) and `hw_id` (the raw word of each wave), with `xcc_id`. Layouts: amdkube.ops.lanecheck."""
+    import numpy as np
+    if block < 0:
+        raise ValueError("block must not be negative")
+    d = dict(_need().lane_check_dump(int(block), seed, device))
+    for k, v in d.items():
+        if k != "xcc_id":
+            d[k] = np.asarray(v).copy()
+    return d

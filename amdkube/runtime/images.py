@@ -59,6 +59,7 @@ def builtin_images() -> dict[str, dict]:
         "amdkube/mfma-check:latest": {"entrypoint": [_b("mfma-check")]},
         "amdkube/cu-check:latest": {"entrypoint": [_b("cu-check")]},
         "amdkube/atomic-check:latest": {"entrypoint": [_b("atomic-check")]},
+        "amdkube/lane-check:latest": {"entrypoint": [_b("lane-check")]},
         "amdkube/xgmi-probe:latest": {"entrypoint": [_b("xgmi-probe")]},
         "busybox:latest": {"entrypoint": [sh]},
         "python:3": {"entrypoint": [py]},

@@ -28,6 +28,8 @@
 //                hbm_plan.h: every bit read in both states, every error with its offset, bits and place
 //   Atomic check (atomic_check.h, behind atomic-check) an order-independent scatter-reduce through the global and
 //                LDS atomic ALUs on the slot map and operands of atomic_plan.h, every slot recomputed without atomics
+//   Lane check   (lane_check.h, behind lane-check) every DPP control, the lane swaps, the LDS crossbar permutes, the
+//                transposing LDS reads and the direct global-to-LDS loads, each result against the map of lane_plan.h
 //   xgmi verify  (xgmi_verify.h, behind xgmi-probe) the fill and count of the all-reduce check, on the
 //                position-hashed values of xgmi_pattern.h
 // The host side is shared: gpu_host.h (AK_HIP, DevInfo, DevBuf, GpuTimer), check_core.h (mix32, calibration,

@@ -3,17 +3,17 @@
   python native/build.py            # CPU-side pybind modules + pause (g++), HIP targets (hipcc, gfx950)
   python native/build.py --cpu-only # just the g++ targets (used by the CPU test tier)
   python native/build.py --sanitize # also the ASan/UBSan host builds (pause, topo self-test, sampler, and the check_core,
-                                    # hbm_plan, atomic_plan, xgmi_pattern, vadd_contract and io_trace self-tests) and the ThreadSanitizer builds of the
+                                    # hbm_plan, atomic_plan, lane_plan, xgmi_pattern, vadd_contract and io_trace self-tests) and the ThreadSanitizer builds of the
                                     # activity sampler, the prefetch and the I/O trace
 
 Outputs: amdkube/_native/{_amdsmi,_topo,_kproto,_quantile,_hipops}.<ext> and amdkube/_native/bin/{pause,
-amdkube-nsexec,amdkube-logpump,sysfs-prefetch-selftest,check-core-selftest,hbm-plan-selftest,atomic-plan-selftest,xgmi-pattern-selftest,
+amdkube-nsexec,amdkube-logpump,sysfs-prefetch-selftest,check-core-selftest,hbm-plan-selftest,atomic-plan-selftest,lane-plan-selftest,xgmi-pattern-selftest,
 vadd-contract-selftest,
-io-trace-selftest,rocm-vector-add,hsa-vector-add,hbm-probe,hbm-check,gpu-burn,mfma-check,cu-check,atomic-check,xgmi-probe[,topo-selftest-asan,
+io-trace-selftest,rocm-vector-add,hsa-vector-add,hbm-probe,hbm-check,gpu-burn,mfma-check,cu-check,atomic-check,lane-check,xgmi-probe[,topo-selftest-asan,
 pause-asan,
 amdkube-nsexec-asan,amdkube-logpump-asan,
 seccomp-check-asan,sampler-selftest-{asan,tsan},sysfs-prefetch-selftest-{asan,tsan},check-core-selftest-asan,
-hbm-plan-selftest-asan,atomic-plan-selftest-asan,xgmi-pattern-selftest-asan,vadd-contract-selftest-asan,io-trace-selftest-{asan,tsan}]}.
+hbm-plan-selftest-asan,atomic-plan-selftest-asan,lane-plan-selftest-asan,xgmi-pattern-selftest-asan,vadd-contract-selftest-asan,io-trace-selftest-{asan,tsan}]}.
 Targets are rebuilt only when a source/header is newer than the output.
 """
 from __future__ import annotations
@@ -53,6 +53,7 @@ def targets(sanitize=False, cpu_only=False):
     trace_selftest = [n("native/io_trace_selftest.cpp"), n("native/io_trace.h"), n("native/sysfs_prefetch.h")]
     plan_selftest = [n("native/hbm_plan_selftest.cpp"), n("kernels/hbm_plan.h"), n("kernels/check_core.h")]
     atomic_selftest = [n("native/atomic_plan_selftest.cpp"), n("kernels/atomic_plan.h"), n("kernels/check_core.h")]
+    lane_selftest = [n("native/lane_plan_selftest.cpp"), n("kernels/lane_plan.h"), n("kernels/check_core.h")]
     xgmi_selftest = [n("native/xgmi_pattern_selftest.cpp"), n("kernels/xgmi_pattern.h"), n("kernels/check_core.h")]
     t = [
         (n(OUT, "_topo" + EXT), [n("native/topo_alloc.cpp"), n("native/topo_core.h")],
@@ -92,6 +93,8 @@ def targets(sanitize=False, cpu_only=False):
         # atomic-check's slot map and its inverse, operands, expected values and the bounds that keep them exact
         (n(BIN, "atomic-plan-selftest"), atomic_selftest,
          ["g++", "-O2", "-std=c++17", "-Wall", atomic_selftest[0], "-o", "{out}"]),
+        # lane-check's source-lane maps, transpose maps and dma sweep against naive loops
+        (n(BIN, "lane-plan-selftest"), lane_selftest, ["g++", "-O2", "-std=c++17", "-Wall", lane_selftest[0], "-o", "{out}"]),
         # xgmi-probe's pattern: the fp32 sum over 1..64 ranks in three orders against the expected value, bit for bit
         (n(BIN, "xgmi-pattern-selftest"), xgmi_selftest, ["g++", "-O2", "-std=c++17", "-Wall", xgmi_selftest[0], "-o", "{out}"]),
         # the pod workload's contract (flags, inputs, verification, grid, output lines) against the two copies it replaced
@@ -135,6 +138,8 @@ def targets(sanitize=False, cpu_only=False):
              ["g++", "-O1", "-std=c++17", *san, plan_selftest[0], "-o", "{out}"]),
             (n(BIN, "atomic-plan-selftest-asan"), atomic_selftest,
              ["g++", "-O1", "-std=c++17", *san, atomic_selftest[0], "-o", "{out}"]),
+            (n(BIN, "lane-plan-selftest-asan"), lane_selftest,
+             ["g++", "-O1", "-std=c++17", *san, lane_selftest[0], "-o", "{out}"]),
             (n(BIN, "xgmi-pattern-selftest-asan"), xgmi_selftest,
              ["g++", "-O1", "-std=c++17", *san, xgmi_selftest[0], "-o", "{out}"]),
             (n(BIN, "vadd-contract-selftest-asan"), vadd_selftest,
@@ -162,8 +167,9 @@ def targets(sanitize=False, cpu_only=False):
         hbm = [n("kernels/hbm_check.h"), n("kernels/hbm_plan.h"), *base]
         xgmi = [n("kernels/xgmi_verify.h"), n("kernels/xgmi_pattern.h"), *base]
         atomic = [n("kernels/atomic_check.h"), n("kernels/atomic_plan.h"), *base]
+        lane = [n("kernels/lane_check.h"), n("kernels/lane_plan.h"), *base]
         t += [
-            (n(OUT, "_hipops" + EXT), [n("native/hipops.hip"), n("kernels/cu_check.h"), *atomic[:2], *hbm[:2], *xgmi[:2], *wide],
+            (n(OUT, "_hipops" + EXT), [n("native/hipops.hip"), n("kernels/cu_check.h"), *atomic[:2], *lane[:2], *hbm[:2], *xgmi[:2], *wide],
              [*ho, "-shared", "-fPIC", *py, n("native/hipops.hip"), "-o", "{out}"]),
             (n(BIN, "rocm-vector-add"), [n("kernels/vector_add.hip"), *base], [*ho, n("kernels/vector_add.hip"), "-o", "{out}"]),
             # the HIP-free pod workload: a bare gfx950 code object, then the HSA host embedding it
@@ -181,6 +187,7 @@ def targets(sanitize=False, cpu_only=False):
             (n(BIN, "mfma-check"), [n("kernels/mfma_check.hip"), *wide], [*ho, n("kernels/mfma_check.hip"), "-o", "{out}"]),
             (n(BIN, "cu-check"), [n("kernels/cu_check.hip"), *cu], [*ho, n("kernels/cu_check.hip"), "-o", "{out}"]),
             (n(BIN, "atomic-check"), [n("kernels/atomic_check.hip"), *atomic], [*ho, n("kernels/atomic_check.hip"), "-o", "{out}"]),
+            (n(BIN, "lane-check"), [n("kernels/lane_check.hip"), *lane], [*ho, n("kernels/lane_check.hip"), "-o", "{out}"]),
             (n(BIN, "xgmi-probe"), [n("kernels/xgmi_probe.cpp"), *xgmi],
              [*ho, "-x", "hip", n("kernels/xgmi_probe.cpp"), *rocm_inc, *rpath, "-lrccl", "-o", "{out}"]),
         ]

@@ -10,6 +10,7 @@
 #include "../kernels/atomic_check.h"
 #include "../kernels/cu_check.h"
 #include "../kernels/hbm_check.h"
+#include "../kernels/lane_check.h"
 #include "../kernels/mfma_check_sparse.h"
 #include "../kernels/xgmi_verify.h"
 
@@ -447,6 +448,74 @@ PYBIND11_MODULE(_hipops, m) {
       },
       py::arg("contention"), py::arg("blocks"), py::arg("seed") = 0x5eedu, py::arg("round") = 0, py::arg("units") = 15,
       py::arg("device") = 0);
+  // the lane check (kernels/lane_check.h): units is a mask over dpp = 1, perm = 2, tr = 4, dma = 8
+  m.def(
+      "lane_check",
+      [](int rounds, double ms, int dev, uint32_t seed, int flips, int units) {
+        const amdkube::LaneCheckResult r = nogil([&] { return amdkube::run_lane_check(rounds, ms, dev, seed, flips, units); });
+        py::dict o, by_unit;
+        py::list units_l, bad, recs;
+        for (int u = 0; u < 4; ++u) {
+          if (r.units & (1 << u)) units_l.append(amdkube::LANE_UNIT_NAMES[u]);
+          by_unit[amdkube::LANE_UNIT_NAMES[u]] = r.errors_by_unit[u];
+        }
+        for (const amdkube::LaneCheckBadCu& b : r.bad_cus) {
+          py::dict d = cu_location(b.where);
+          d["errors"] = b.errors;
+          bad.append(d);
+        }
+        for (const amdkube::LaneCheckRecord& e : r.first_errors) {
+          py::dict d = cu_location(amdkube::cu_decode_location(e.hw_id, e.xcc_id));
+          d["simd"] = amdkube::lane_simd_of(e.hw_id);
+          d["unit"] = amdkube::LANE_UNIT_NAMES[e.unit < 4 ? e.unit : 0];
+          d["block"] = e.block;
+          d["round"] = e.round;
+          d["op"] = e.op;
+          d["lane"] = e.lane;
+          d["got"] = e.got;
+          d["want"] = e.want;
+          recs.append(d);
+        }
+        o["ok"] = r.errors == 0;
+        o["errors"] = r.errors;
+        o["errors_by_unit"] = by_unit;
+        o["units"] = units_l;
+        o["rounds"] = r.rounds;
+        o["blocks"] = r.blocks;
+        o["launches"] = r.launches;
+        o["ms"] = r.ms;
+        o["xlane_gops"] = r.xlane_gops;
+        o["tr_gbps"] = r.tr_gbps;
+        o["dma_gbps"] = r.dma_gbps;
+        o["cus"] = r.cus;
+        o["cus_covered"] = r.cus_covered;
+        o["simds"] = r.simds;
+        o["simds_covered"] = r.simds_covered;
+        o["xccs"] = r.xccs;
+        // raw HW_ID of the 16 waves, then XCC_ID, of every workgroup of the timed launch
+        o["block_loc"] = py::array_t<uint32_t>({static_cast<py::ssize_t>(r.blocks), static_cast<py::ssize_t>(amdkube::LANE_LOC_WORDS)},
+                                               r.block_loc.data());
+        o["bad_cus"] = bad;
+        o["first_errors"] = recs;
+        return o;
+      },
+      py::arg("rounds") = 0, py::arg("ms") = 50.0, py::arg("device") = 0, py::arg("seed") = 0x5eedu,
+      py::arg("selftest_flips") = 0, py::arg("units") = 15);
+  m.def(
+      "lane_check_dump",
+      [](int block, uint32_t seed, int dev) {
+        const amdkube::LaneCheckDump d = nogil([&] { return amdkube::lane_check_dump_host(block, seed, dev); });
+        const py::ssize_t T = amdkube::LANE_THREADS;
+        py::dict o;
+        o["dpp"] = py::array_t<uint32_t>({T, static_cast<py::ssize_t>(amdkube::LANE_DPP_OPS)}, d.dpp.data());
+        o["perm"] = py::array_t<uint32_t>({T, static_cast<py::ssize_t>(amdkube::LANE_PERM_OPS)}, d.perm.data());
+        o["tr"] = py::array_t<uint32_t>({T, static_cast<py::ssize_t>(amdkube::LANE_TR_REG_TOTAL)}, d.tr.data());
+        o["dma"] = py::array_t<uint32_t>(d.dma.size(), d.dma.data());
+        o["hw_id"] = py::array_t<uint32_t>(d.hw_id.size(), d.hw_id.data());
+        o["xcc_id"] = d.xcc_id;
+        return o;
+      },
+      py::arg("block"), py::arg("seed") = 0x5eedu, py::arg("device") = 0);
   // the HBM march (kernels/hbm_check.h): mib == 0 and free_fraction == 0 mean "not given"
   m.def(
       "hbm_check",
