@@ -403,18 +403,6 @@ __global__ __launch_bounds__(ATOMIC_WG) void atomic_verify_kernel(AtomicArgs a) 
 // ---------------------------------------------------------------------------- runners
 constexpr const char* ATOMIC_UNIT_NAMES[4] = {"int", "fp", "ret", "lds"};
 
-// "int,fp,ret,lds" -> mask; throws std::invalid_argument on an unknown or empty name
-inline int atomic_check_units(const std::string& list) {
-  int mask = 0;
-  for (const std::string& name : split_list(list)) {
-    int u = 0;
-    while (u < 4 && name != ATOMIC_UNIT_NAMES[u]) ++u;
-    if (u == 4) throw std::invalid_argument("unknown unit '" + name + "': expected a comma list over int, fp, ret, lds");
-    mask |= 1 << u;
-  }
-  return mask;
-}
-
 // c = 1 spreads over every slot and so every L2 channel, 64 is one wave's worth on a slot, 4096 is heavy
 inline std::vector<uint32_t> atomic_default_contention() { return {1u, 64u, 4096u}; }
 
@@ -579,14 +567,7 @@ inline AtomicCheckResult run_atomic_check(int rounds, double target_ms, int dev,
         });
       },
       2, 1 << 16, rounds, target_ms, flips);
-  const std::vector<unsigned long long> by_unit = run.errors.download<unsigned long long>();
-  for (int u = 0; u < 4; ++u) {
-    r.errors_by_unit[u] = by_unit[u];
-    r.errors += by_unit[u];
-  }
-  r.first_errors = fetch_records<AtomicRecord>(run.nrec, run.recs);
-  r.ms = c.ms;
-  r.rounds = c.rounds;
+  fetch_outcome(r, c, run.errors, run.nrec, run.recs);
   r.blocks = blocks;
   r.units = units;
   r.contention = contention;

@@ -48,9 +48,7 @@
 // bits [31:4] read 0. One launch of 4 workgroups per CU covered every CU in the runs measured.
 #pragma once
 
-#include <map>
-#include <set>
-
+#include "cu_run.h"
 #include "gpu_common.h"
 
 namespace amdkube {
@@ -70,7 +68,7 @@ constexpr int CU_CHECK_TRANS_N = CU_CHECK_TRANS_FUNCS * CU_CHECK_TRANS_SETS;  //
 constexpr int CU_CHECK_VALU_OPS = 12;   // dumped operand words per lane: a0 b0 c0 a1 b1 c1 wa wb wc x m k
 constexpr int CU_CHECK_VALU_MADS = 2 + 2 + 2 + 2 + 2 + CU_CHECK_CHAIN;  // multiply-adds per lane and round
 enum : int { CU_UNIT_LDS = 1, CU_UNIT_VALU = 2, CU_UNIT_TRANS = 4, CU_UNIT_ALL = 7 };
-// (CU_HWREG_HW_ID, CU_HWREG_XCC_ID, CuLocation and cu_decode_location: gpu_common.h, shared with hbm_check.h)
+// (CU_HWREG_HW_ID, CU_HWREG_XCC_ID: gpu_common.h; CuLocation and cu_decode_location: check_core.h)
 
 // unit: 0 lds, 1 valu, 2 trans; hw_id and xcc_id are the raw words of the wave that saw the mismatch.
 // lds: index is the LDS byte address and pass the march pass (2, 3 or 4). valu: index is
@@ -462,66 +460,21 @@ __global__ __launch_bounds__(CU_CHECK_THREADS) void cu_check_kernel(CuCheckArgs 
 }
 
 // ---------------------------------------------------------------------------- runners
-inline int cu_check_blocks(int cu_count) { return (cu_count > 0 ? cu_count : 256) * CU_CHECK_BLOCKS_PER_CU; }
+static_assert(CU_CHECK_LDS_BYTES == CU_RUN_LDS_BYTES && CU_CHECK_BLOCKS_PER_CU == CU_RUN_BLOCKS_PER_CU &&
+                  CU_CHECK_RECORDS == CU_RUN_RECORDS, "the kernel is launched and read back by cu_run.h");
 
 // unit u has the mask bit 1 << u and the number u in a record
 constexpr const char* CU_UNIT_NAMES[3] = {"lds", "valu", "trans"};
 
-// "lds,valu,trans" -> mask; throws std::invalid_argument on an unknown or empty name
-inline int cu_check_units(const std::string& list) {
-  int mask = 0;
-  for (const std::string& name : split_list(list)) {
-    int u = 0;
-    while (u < 3 && name != CU_UNIT_NAMES[u]) ++u;
-    if (u == 3) throw std::invalid_argument("unknown unit '" + name + "': expected a comma list over lds, valu, trans");
-    mask |= 1 << u;
-  }
-  return mask;
-}
-
-struct CuCheckBadCu {
-  CuLocation where;
-  unsigned long long errors = 0;
-};
-
-struct CuCheckResult {
-  double ms = 0, lds_gbps = 0, valu_gops = 0;
-  long long rounds = 0;
-  int blocks = 0, units = 0, launches = 0;
-  int cus = 0, cus_covered = 0, xccs = 0;
-  unsigned long long errors = 0, errors_by_unit[3] = {0, 0, 0};
+struct CuCheckResult : CuRunResult<CuCheckRecord, 3> {
+  double lds_gbps = 0, valu_gops = 0;
   std::vector<CuLocation> locations;      // the distinct places seen over all launches, sorted
-  std::vector<uint32_t> block_loc;        // [blocks][2] raw HW_ID, XCC_ID of the timed launch
-  std::vector<CuCheckBadCu> bad_cus;      // at most 16
-  std::vector<CuCheckRecord> first_errors;
 };
 
-// Device buffers and the launch of one check; errors and records accumulate over launches, the
-// places and per-workgroup error counts are collected after each launch.
-struct CuCheckRun {
-  int cus, blocks, units;
-  uint32_t seed;
-  DevBuf errors, block_errors, nrec, recs, flip_pos, loc;
-  std::set<uint32_t> seen;
-  std::map<uint32_t, unsigned long long> bad;
-  std::vector<uint32_t> block_loc;
-  int launches = 0;
+// block_loc is [blocks][2]: the raw HW_ID of wave 0, then XCC_ID
+struct CuCheckRun : CuRun {
   CuCheckRun(int dev, uint32_t seed_, int units_)
-      : cus(dev_info(dev).cu_count), blocks(cu_check_blocks(cus)), units(checked_units(units_)), seed(seed_),
-        errors(3 * sizeof(unsigned long long), DevBuf::zeroed), block_errors(blocks * sizeof(unsigned), DevBuf::zeroed),
-        nrec(sizeof(unsigned), DevBuf::zeroed), recs(CU_CHECK_RECORDS * sizeof(CuCheckRecord), DevBuf::zeroed),
-        flip_pos(flip_table(seed_, blocks, units)), loc(blocks * 2 * sizeof(uint32_t), DevBuf::zeroed),
-        block_loc(static_cast<size_t>(blocks) * 2) {
-    hipDeviceProp_t p;
-    AK_HIP(hipGetDeviceProperties(&p, dev));
-    if (p.sharedMemPerBlock < static_cast<size_t>(CU_CHECK_LDS_BYTES))
-      throw std::runtime_error("cu-check needs 163840 bytes of LDS per workgroup, the device offers " +
-                               std::to_string(p.sharedMemPerBlock));
-  }
-  static int checked_units(int units) {
-    if (units < 1 || units > CU_UNIT_ALL) throw std::invalid_argument("units must name at least one of lds, valu, trans");
-    return units;
-  }
+      : CuRun("cu-check", dev, seed_, units_, CU_UNIT_NAMES, 3, sizeof(CuCheckRecord), 1, flip_table) {}
   // Flip i belongs to unit slot i mod n_en; its position is (base + i * stride) mod (blocks * elems) of
   // that unit, elems = 40960 words (lds) or 1024 lanes (valu, trans). The stride is coprime to
   // both moduli (the smaller divides the larger), so the positions of one unit are distinct.
@@ -533,111 +486,26 @@ struct CuCheckRun {
       if (units & (1 << u)) slot_mod.push_back(u == 0 ? large : small);
     return flip_positions(seed, CU_CHECK_MAX_FLIPS, small, large, slot_mod);
   }
-  CuCheckArgs args(int rounds, int flips) const {
-    CuCheckArgs a = {};
-    a.seed = seed;
-    a.rounds = rounds;
-    a.flips = flips;
-    a.units = units;
-    a.dbg_block = -1;
-    a.flip_pos = flip_pos.as<const uint32_t>();
-    a.errors = errors.as<unsigned long long>();
-    a.block_errors = block_errors.as<unsigned>();
-    a.nrec = nrec.as<unsigned>();
-    a.recs = recs.as<CuCheckRecord>();
-    a.loc = loc.as<uint32_t>();
-    return a;
-  }
-  void launch(const CuCheckArgs& a) {
-    hipLaunchKernelGGL(cu_check_kernel, dim3(blocks), dim3(CU_CHECK_THREADS), 0, 0, a);
-    AK_HIP(hipGetLastError());
-    ++launches;
-  }
-  // after a finished launch: where its workgroups ran, and which of them counted errors
-  void collect() {
-    block_loc = loc.download<uint32_t>();
-    const std::vector<unsigned> be = block_errors.download<unsigned>();
-    bool any = false;
-    for (int b = 0; b < blocks; ++b) {
-      const uint32_t key = cu_decode_location(block_loc[2 * b], block_loc[2 * b + 1]).key();
-      seen.insert(key);
-      if (be[b]) {
-        bad[key] += be[b];
-        any = true;
-      }
-    }
-    if (any) block_errors.zero();
+  CuCheckArgs args(int rounds, int flips) const { return CuRun::args<CuCheckArgs>(rounds, flips); }
+  void launch(const CuCheckArgs& a) { CuRun::launch(cu_check_kernel, CU_CHECK_THREADS, a); }
+  bool covered() const { return coverage.cus_covered() >= cus; }
+  // rates of the timed launch over its whole time: a unit's own rate when it runs alone
+  void finish(CuCheckResult& r, const Calibrated& c) const {
+    r.locations = coverage.locations();
+    const double per_s = static_cast<double>(blocks) * c.rounds / (c.ms * 1e-3);
+    if (units & CU_UNIT_LDS) r.lds_gbps = per_s * 6.0 * CU_CHECK_LDS_BYTES / 1e9;  // three store and three load passes
+    if (units & CU_UNIT_VALU) r.valu_gops = per_s * CU_CHECK_THREADS * CU_CHECK_VALU_MADS / 1e9;
   }
 };
 
-inline CuLocation cu_location_of_key(uint32_t key) {
-  CuLocation l;
-  l.xcc = key >> 12;
-  l.se = (key >> 8) & 15;
-  l.sh = (key >> 4) & 15;
-  l.cu = key & 15;
-  return l;
-}
-
-// rounds > 0: one launch of exactly that many rounds. rounds <= 0: calibrated to ~target_ms
-// (check_core.h; the self-test flips go into the last launch only).
-inline CuCheckResult cu_check_drive(CuCheckRun& run, int rounds, double target_ms, int flips) {
-  GpuTimer timer;
-  const Calibrated c = calibrate(
-      [&](int r, int f) {
-        const double ms = timer.time([&] { run.launch(run.args(r, f)); });
-        run.collect();
-        return ms;
-      },
-      16, 1 << 26, rounds, target_ms, flips);
-  CuCheckResult r;
-  const std::vector<unsigned long long> by_unit = run.errors.download<unsigned long long>();
-  for (int u = 0; u < 3; ++u) r.errors_by_unit[u] = by_unit[u];
-  r.first_errors = fetch_records<CuCheckRecord>(run.nrec, run.recs);
-  r.errors = r.errors_by_unit[0] + r.errors_by_unit[1] + r.errors_by_unit[2];
-  r.ms = c.ms;
-  r.rounds = c.rounds;
-  r.blocks = run.blocks;
-  r.units = run.units;
-  r.launches = run.launches;
-  r.cus = run.cus;
-  r.cus_covered = static_cast<int>(run.seen.size());
-  std::set<int> xccs;
-  for (uint32_t key : run.seen) {
-    r.locations.push_back(cu_location_of_key(key));
-    xccs.insert(static_cast<int>(key >> 12));
-  }
-  r.xccs = static_cast<int>(xccs.size());
-  r.block_loc = run.block_loc;
-  for (const auto& kv : run.bad) {
-    if (r.bad_cus.size() == static_cast<size_t>(CU_CHECK_RECORDS)) break;
-    r.bad_cus.push_back(CuCheckBadCu{cu_location_of_key(kv.first), kv.second});
-  }
-  // rates of the last launch over its whole time: a unit's own rate when it runs alone
-  const double per_s = static_cast<double>(run.blocks) * c.rounds / (c.ms * 1e-3);
-  if (run.units & CU_UNIT_LDS) r.lds_gbps = per_s * 6.0 * CU_CHECK_LDS_BYTES / 1e9;  // three store and three load passes
-  if (run.units & CU_UNIT_VALU) r.valu_gops = per_s * CU_CHECK_THREADS * CU_CHECK_VALU_MADS / 1e9;
-  return r;
-}
-
-// Runs the check; while the places seen are fewer than the device's CUs, up to CU_CHECK_EXTRA_LAUNCHES
-// further launches of one round each are added (they check as well, and count into errors).
+// Runs the check (cu_run.h); while the places seen are fewer than the device's CUs, up to
+// CU_CHECK_EXTRA_LAUNCHES further launches of one round each are added.
 inline CuCheckResult run_cu_check(int rounds, double target_ms, int dev, uint32_t seed = 0x5eedu, int flips = 0,
                                   int units = CU_UNIT_ALL) {
   if (flips < 0 || flips > CU_CHECK_MAX_FLIPS) throw std::invalid_argument("selftest flips must be in [0, 4096]");
   AK_HIP(hipSetDevice(dev));
   CuCheckRun run(dev, seed, units);
-  CuCheckResult r = cu_check_drive(run, rounds, target_ms, flips);
-  if (r.cus_covered < r.cus) {
-    const CuCheckResult first = r;
-    for (int i = 0; i < CU_CHECK_EXTRA_LAUNCHES && r.cus_covered < r.cus; ++i) r = cu_check_drive(run, 1, 0, 0);
-    r.ms = first.ms;  // the timed launch stays the reported one, with the places of its workgroups
-    r.block_loc = first.block_loc;
-    r.rounds = first.rounds;
-    r.lds_gbps = first.lds_gbps;
-    r.valu_gops = first.valu_gops;
-  }
-  return r;
+  return cu_run<CuCheckResult>(run, rounds, target_ms, flips, CU_CHECK_EXTRA_LAUNCHES);
 }
 
 struct CuCheckDump {

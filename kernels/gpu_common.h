@@ -32,10 +32,12 @@
 //                transposing LDS reads and the direct global-to-LDS loads, each result against the map of lane_plan.h
 //   xgmi verify  (xgmi_verify.h, behind xgmi-probe) the fill and count of the all-reduce check, on the
 //                position-hashed values of xgmi_pattern.h
-// The host side is shared: gpu_host.h (AK_HIP, DevInfo, DevBuf, GpuTimer), check_core.h (mix32, calibration,
-// self-test flip positions, list splitting) and vadd_contract.h (the pod workload's contract, which
-// hsa-vector-add shares: flags, inputs, verification, stream_grid, output lines, exit codes); the last
-// two are plain C++, self-tested on the CPU.
+// The host side is shared: gpu_host.h (AK_HIP, DevInfo, DevBuf, GpuTimer, fetch_outcome), check_core.h (mix32,
+// calibration, self-test flip positions, unit lists, CuLocation, CuCoverage), cu_run.h (the buffers and the run
+// of the checks that own their CU), check_cli.h (the check programs' flags and the JSON pieces they share) and
+// vadd_contract.h (the pod workload's contract, which hsa-vector-add shares: flags, inputs, verification,
+// stream_grid, output lines, exit codes); check_core.h, check_cli.h and vadd_contract.h are plain C++,
+// self-tested on the CPU.
 //
 // Every launch is bounded by construction (grid-stride loops over checked sizes) and uses
 // no inter-workgroup synchronisation, so no launch can hang the device.
@@ -71,24 +73,10 @@ __global__ __launch_bounds__(VADD_WG) void vadd_kernel(const float* __restrict__
 // (mix32, one- and three-argument, for host and device: check_core.h)
 
 // Where a wave runs: the raw HW_ID and XCC_ID words (the field layout and what an MI355X shows in them:
-// cu_check.h) and their decoding into (xcc, se, sh, cu). For the checks that say where an error was seen.
+// cu_check.h; their decoding into (xcc, se, sh, cu): CuLocation, check_core.h).
 // s_getreg_b32 operand: register id, offset 0, all 32 bits
 constexpr int CU_HWREG_HW_ID = 4 | (31 << 11);
 constexpr int CU_HWREG_XCC_ID = 20 | (31 << 11);
-
-struct CuLocation {
-  int xcc = 0, se = 0, sh = 0, cu = 0;
-  uint32_t key() const { return static_cast<uint32_t>(xcc) << 12 | se << 8 | sh << 4 | cu; }
-};
-
-inline CuLocation cu_decode_location(uint32_t hw_id, uint32_t xcc_id) {
-  CuLocation l;
-  l.xcc = xcc_id & 15u;
-  l.cu = (hw_id >> 8) & 15u;
-  l.sh = (hw_id >> 12) & 1u;
-  l.se = (hw_id >> 13) & 7u;
-  return l;
-}
 
 __device__ __forceinline__ uint4 pattern(size_t i, uint32_t seed) {
   uint32_t base = static_cast<uint32_t>(i * 4) ^ seed ^ static_cast<uint32_t>(i >> 30);

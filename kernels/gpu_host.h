@@ -1,6 +1,7 @@
 // HIP host plumbing of the validation workloads: error checking, device identity, and the owners of
 // device buffers and events, so that a thrown AK_HIP frees what a runner had allocated (the extension
 // _hipops lives as long as its process). The only place that allocates or frees device memory and events.
+// fetch_records and fetch_outcome read back what every check leaves on the device.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -10,6 +11,8 @@
 #include <stdexcept>
 #include <string>
 #include <vector>
+
+#include "check_core.h"
 
 namespace amdkube {
 
@@ -118,6 +121,21 @@ struct GpuTimer {
 template <class Rec>
 inline std::vector<Rec> fetch_records(const DevBuf& nrec, const DevBuf& recs) {
   return recs.download<Rec>(nrec.download<unsigned>()[0]);
+}
+
+// What a check reads back after its last launch, into the fields every result has: the error count of each
+// unit (`errors` holds one per element of r.errors_by_unit), their sum, the first records, and the time and
+// round count of the last timed launch.
+template <class Result>
+inline void fetch_outcome(Result& r, const Calibrated& c, const DevBuf& errors, const DevBuf& nrec, const DevBuf& recs) {
+  const std::vector<unsigned long long> by_unit = errors.download<unsigned long long>();
+  for (size_t u = 0; u < by_unit.size(); ++u) {
+    r.errors_by_unit[u] = by_unit[u];
+    r.errors += by_unit[u];
+  }
+  r.first_errors = fetch_records<typename decltype(r.first_errors)::value_type>(nrec, recs);
+  r.ms = c.ms;
+  r.rounds = c.rounds;
 }
 
 }  // namespace amdkube

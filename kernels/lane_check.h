@@ -40,10 +40,9 @@
 // address as well as the LDS address.
 #pragma once
 
-#include <map>
-#include <set>
 #include <utility>
 
+#include "cu_run.h"
 #include "gpu_common.h"
 #include "lane_plan.h"
 
@@ -446,64 +445,24 @@ __global__ __launch_bounds__(LANE_THREADS) void lane_check_kernel(LaneCheckArgs 
 }
 
 // ---------------------------------------------------------------------------- runners
-inline int lane_check_blocks(int cu_count) { return (cu_count > 0 ? cu_count : 256) * LANE_BLOCKS_PER_CU; }
+static_assert(LANE_LDS_BYTES == CU_RUN_LDS_BYTES && LANE_BLOCKS_PER_CU == CU_RUN_BLOCKS_PER_CU && LANE_RECORDS == CU_RUN_RECORDS,
+              "the kernel is launched and read back by cu_run.h");
 
 // unit u has the mask bit 1 << u and the number u in a record
 constexpr const char* LANE_UNIT_NAMES[4] = {"dpp", "perm", "tr", "dma"};
 constexpr unsigned long long LANE_UNIT_ELEMS[4] = {LANE_THREADS, LANE_THREADS, LANE_THREADS, LANE_WORDS};
 
-// "dpp,tr" -> mask; throws std::invalid_argument on an unknown or empty name
-inline int lane_check_units(const std::string& list) {
-  int mask = 0;
-  for (const std::string& name : split_list(list)) {
-    int u = 0;
-    while (u < 4 && name != LANE_UNIT_NAMES[u]) ++u;
-    if (u == 4) throw std::invalid_argument("unknown unit '" + name + "': expected a comma list over dpp, perm, tr, dma");
-    mask |= 1 << u;
-  }
-  return mask;
-}
-
-inline int lane_simd_of(uint32_t hw_id) { return static_cast<int>((hw_id >> 4) & 3u); }
-
-struct LaneCheckBadCu {
-  CuLocation where;
-  unsigned long long errors = 0;
+struct LaneCheckResult : CuRunResult<LaneCheckRecord, 4> {
+  double xlane_gops = 0, tr_gbps = 0, dma_gbps = 0;
+  int simds = 0, simds_covered = 0;
 };
 
-struct LaneCheckResult {
-  double ms = 0, xlane_gops = 0, tr_gbps = 0, dma_gbps = 0;
-  long long rounds = 0;
-  int blocks = 0, units = 0, launches = 0;
-  int cus = 0, cus_covered = 0, simds = 0, simds_covered = 0, xccs = 0;
-  unsigned long long errors = 0, errors_by_unit[4] = {0, 0, 0, 0};
-  std::vector<uint32_t> block_loc;        // [blocks][LANE_LOC_WORDS] raw words of the timed launch
-  std::vector<LaneCheckBadCu> bad_cus;    // at most 16
-  std::vector<LaneCheckRecord> first_errors;
-};
-
-// Device buffers and the launch of one check; errors and records accumulate over launches, the places and
-// per-workgroup error counts are collected after each launch.
-struct LaneCheckRun {
-  int cus, blocks, units;
-  uint32_t seed;
-  DevBuf errors, block_errors, nrec, recs, flip_pos, loc, src;
-  std::set<uint32_t> seen_cus, seen_simds;
-  std::map<uint32_t, unsigned long long> bad;
-  std::vector<uint32_t> block_loc;
-  int launches = 0;
+// block_loc is [blocks][LANE_LOC_WORDS]; src is the dma unit's source
+struct LaneCheckRun : CuRun {
+  DevBuf src;
   LaneCheckRun(int dev, uint32_t seed_, int units_)
-      : cus(dev_info(dev).cu_count), blocks(lane_check_blocks(cus)), units(checked_units(units_)), seed(seed_),
-        errors(4 * sizeof(unsigned long long), DevBuf::zeroed), block_errors(blocks * sizeof(unsigned), DevBuf::zeroed),
-        nrec(sizeof(unsigned), DevBuf::zeroed), recs(LANE_RECORDS * sizeof(LaneCheckRecord), DevBuf::zeroed),
-        flip_pos(flip_table(seed_, blocks, units)), loc(blocks * LANE_LOC_WORDS * sizeof(uint32_t), DevBuf::zeroed),
-        src(units & LANE_UNIT_DMA ? source_words() * sizeof(uint32_t) : 0),
-        block_loc(static_cast<size_t>(blocks) * LANE_LOC_WORDS) {
-    hipDeviceProp_t p;
-    AK_HIP(hipGetDeviceProperties(&p, dev));
-    if (p.sharedMemPerBlock < static_cast<size_t>(LANE_LDS_BYTES))
-      throw std::runtime_error("lane-check needs 163840 bytes of LDS per workgroup, the device offers " +
-                               std::to_string(p.sharedMemPerBlock));
+      : CuRun("lane-check", dev, seed_, units_, LANE_UNIT_NAMES, 4, sizeof(LaneCheckRecord), LANE_WAVES, flip_table),
+        src(units & LANE_UNIT_DMA ? source_words() * sizeof(uint32_t) : 0) {
     if (units & LANE_UNIT_DMA) {  // a launch of its own: the check relies on no visibility between workgroups
       hipLaunchKernelGGL(lane_dma_fill_kernel, dim3(blocks), dim3(256), 0, 0, src.as<uint32_t>(), source_words(),
                          lane_dma_source_key(seed));
@@ -512,10 +471,6 @@ struct LaneCheckRun {
     }
   }
   size_t source_words() const { return static_cast<size_t>(blocks) * LANE_WORDS + LANE_SRC_PAD; }
-  static int checked_units(int units) {
-    if (units < 1 || units > LANE_UNIT_ALL) throw std::invalid_argument("units must name at least one of dpp, perm, tr, dma");
-    return units;
-  }
   // Flip i belongs to unit slot i mod n_en; its position is (base + i * stride) mod (blocks * elems) of that
   // unit, elems = 1024 lanes (dpp, perm, tr) or 40960 words (dma): check_core.h keeps them distinct.
   static std::vector<uint32_t> flip_table(uint32_t seed, int blocks, int units) {
@@ -526,117 +481,32 @@ struct LaneCheckRun {
                           static_cast<unsigned long long>(blocks) * LANE_WORDS, slot_mod);
   }
   LaneCheckArgs args(int rounds, int flips) const {
-    LaneCheckArgs a = {};
-    a.seed = seed;
-    a.rounds = rounds;
-    a.flips = flips;
-    a.units = units;
-    a.dbg_block = -1;
-    a.flip_pos = flip_pos.as<const uint32_t>();
+    LaneCheckArgs a = CuRun::args<LaneCheckArgs>(rounds, flips);
     a.src = src.as<const uint32_t>();
-    a.errors = errors.as<unsigned long long>();
-    a.block_errors = block_errors.as<unsigned>();
-    a.nrec = nrec.as<unsigned>();
-    a.recs = recs.as<LaneCheckRecord>();
-    a.loc = loc.as<uint32_t>();
     return a;
   }
-  void launch(const LaneCheckArgs& a) {
-    hipLaunchKernelGGL(lane_check_kernel, dim3(blocks), dim3(LANE_THREADS), 0, 0, a);
-    AK_HIP(hipGetLastError());
-    ++launches;
-  }
-  // after a finished launch: where its waves ran, and which workgroups counted errors
-  void collect() {
-    block_loc = loc.download<uint32_t>();
-    const std::vector<unsigned> be = block_errors.download<unsigned>();
-    bool any = false;
-    for (int b = 0; b < blocks; ++b) {
-      const uint32_t* w = &block_loc[static_cast<size_t>(b) * LANE_LOC_WORDS];
-      const uint32_t key = cu_decode_location(w[0], w[LANE_WAVES]).key();
-      seen_cus.insert(key);
-      for (int v = 0; v < LANE_WAVES; ++v) seen_simds.insert(cu_decode_location(w[v], w[LANE_WAVES]).key() << 2 | lane_simd_of(w[v]));
-      if (be[b]) {
-        bad[key] += be[b];
-        any = true;
-      }
-    }
-    if (any) block_errors.zero();
+  void launch(const LaneCheckArgs& a) { CuRun::launch(lane_check_kernel, LANE_THREADS, a); }
+  bool covered() const { return coverage.simds_covered() >= 4 * cus; }
+  // rates of the timed launch over its whole time: a unit's own rate when it runs alone
+  void finish(LaneCheckResult& r, const Calibrated& c) const {
+    r.simds = 4 * cus;
+    r.simds_covered = coverage.simds_covered();
+    const double per_s = static_cast<double>(blocks) * c.rounds / (c.ms * 1e-3);
+    const int xlane_ops = (units & LANE_UNIT_DPP ? LANE_DPP_OPS : 0) + (units & LANE_UNIT_PERM ? LANE_PERM_OPS : 0);
+    r.xlane_gops = per_s * LANE_THREADS * xlane_ops / 1e9;
+    if (units & LANE_UNIT_TR) r.tr_gbps = per_s * LANE_THREADS * LANE_TR_BYTES_PER_LANE / 1e9;
+    if (units & LANE_UNIT_DMA) r.dma_gbps = per_s * (LANE_DMA_BYTES_3_ROUNDS / 3.0) / 1e9;  // bytes landed in LDS
   }
 };
 
-inline CuLocation lane_location_of_key(uint32_t key) {
-  CuLocation l;
-  l.xcc = key >> 12;
-  l.se = (key >> 8) & 15;
-  l.sh = (key >> 4) & 15;
-  l.cu = key & 15;
-  return l;
-}
-
-// rounds > 0: one launch of exactly that many rounds. rounds <= 0: calibrated to ~target_ms
-// (check_core.h; the self-test flips go into the last launch only).
-inline LaneCheckResult lane_check_drive(LaneCheckRun& run, int rounds, double target_ms, int flips) {
-  GpuTimer timer;
-  const Calibrated c = calibrate(
-      [&](int r, int f) {
-        const double ms = timer.time([&] { run.launch(run.args(r, f)); });
-        run.collect();
-        return ms;
-      },
-      16, 1 << 26, rounds, target_ms, flips);
-  LaneCheckResult r;
-  const std::vector<unsigned long long> by_unit = run.errors.download<unsigned long long>();
-  for (int u = 0; u < 4; ++u) {
-    r.errors_by_unit[u] = by_unit[u];
-    r.errors += by_unit[u];
-  }
-  r.first_errors = fetch_records<LaneCheckRecord>(run.nrec, run.recs);
-  r.ms = c.ms;
-  r.rounds = c.rounds;
-  r.blocks = run.blocks;
-  r.units = run.units;
-  r.launches = run.launches;
-  r.cus = run.cus;
-  r.simds = 4 * run.cus;
-  r.cus_covered = static_cast<int>(run.seen_cus.size());
-  r.simds_covered = static_cast<int>(run.seen_simds.size());
-  std::set<int> xccs;
-  for (uint32_t key : run.seen_cus) xccs.insert(static_cast<int>(key >> 12));
-  r.xccs = static_cast<int>(xccs.size());
-  r.block_loc = run.block_loc;
-  for (const auto& kv : run.bad) {
-    if (r.bad_cus.size() == static_cast<size_t>(LANE_RECORDS)) break;
-    r.bad_cus.push_back(LaneCheckBadCu{lane_location_of_key(kv.first), kv.second});
-  }
-  // rates of the last launch over its whole time: a unit's own rate when it runs alone
-  const double per_s = static_cast<double>(run.blocks) * c.rounds / (c.ms * 1e-3);
-  const int xlane_ops = (run.units & LANE_UNIT_DPP ? LANE_DPP_OPS : 0) + (run.units & LANE_UNIT_PERM ? LANE_PERM_OPS : 0);
-  r.xlane_gops = per_s * LANE_THREADS * xlane_ops / 1e9;
-  if (run.units & LANE_UNIT_TR) r.tr_gbps = per_s * LANE_THREADS * LANE_TR_BYTES_PER_LANE / 1e9;
-  if (run.units & LANE_UNIT_DMA) r.dma_gbps = per_s * (LANE_DMA_BYTES_3_ROUNDS / 3.0) / 1e9;  // bytes landed in LDS
-  return r;
-}
-
-// Runs the check; while the SIMDs seen are fewer than four to a CU, up to LANE_EXTRA_LAUNCHES further launches
-// of one round each are added (they check as well, and count into errors).
+// Runs the check (cu_run.h); while the SIMDs seen are fewer than four to a CU, up to LANE_EXTRA_LAUNCHES
+// further launches of one round each are added.
 inline LaneCheckResult run_lane_check(int rounds, double target_ms, int dev, uint32_t seed = 0x5eedu, int flips = 0,
                                       int units = LANE_UNIT_ALL) {
   if (flips < 0 || flips > LANE_MAX_FLIPS) throw std::invalid_argument("selftest flips must be in [0, 4096]");
   AK_HIP(hipSetDevice(dev));
   LaneCheckRun run(dev, seed, units);
-  LaneCheckResult r = lane_check_drive(run, rounds, target_ms, flips);
-  if (r.simds_covered < r.simds) {
-    const LaneCheckResult first = r;
-    for (int i = 0; i < LANE_EXTRA_LAUNCHES && r.simds_covered < r.simds; ++i) r = lane_check_drive(run, 1, 0, 0);
-    r.ms = first.ms;  // the timed launch stays the reported one, with the places of its waves
-    r.block_loc = first.block_loc;
-    r.rounds = first.rounds;
-    r.xlane_gops = first.xlane_gops;
-    r.tr_gbps = first.tr_gbps;
-    r.dma_gbps = first.dma_gbps;
-  }
-  return r;
+  return cu_run<LaneCheckResult>(run, rounds, target_ms, flips, LANE_EXTRA_LAUNCHES);
 }
 
 struct LaneCheckDump {

@@ -51,6 +51,7 @@ def targets(sanitize=False, cpu_only=False):
     n = lambda *p: os.path.join(ROOT, *p)  # noqa: E731
     vadd_selftest = [n("native/vadd_contract_selftest.cpp"), n("kernels/vadd_contract.h")]
     trace_selftest = [n("native/io_trace_selftest.cpp"), n("native/io_trace.h"), n("native/sysfs_prefetch.h")]
+    core_selftest = [n("native/check_core_selftest.cpp"), n("kernels/check_core.h"), n("kernels/check_cli.h")]
     plan_selftest = [n("native/hbm_plan_selftest.cpp"), n("kernels/hbm_plan.h"), n("kernels/check_core.h")]
     atomic_selftest = [n("native/atomic_plan_selftest.cpp"), n("kernels/atomic_plan.h"), n("kernels/check_core.h")]
     lane_selftest = [n("native/lane_plan_selftest.cpp"), n("kernels/lane_plan.h"), n("kernels/check_core.h")]
@@ -85,9 +86,10 @@ def targets(sanitize=False, cpu_only=False):
         # the KFD-topology prefetch of hsa-vector-add, checked on a fake tree through its own fopen
         (n(BIN, "sysfs-prefetch-selftest"), [n("native/sysfs_prefetch_selftest.cpp"), n("native/sysfs_prefetch.h")],
          ["g++", "-O2", "-std=c++17", "-Wall", n("native/sysfs_prefetch_selftest.cpp"), "-pthread", "-ldl", "-o", "{out}"]),
-        # the calibration, flip positions and list splitting of the GPU checks, against the loops they replaced
-        (n(BIN, "check-core-selftest"), [n("native/check_core_selftest.cpp"), n("kernels/check_core.h")],
-         ["g++", "-O2", "-std=c++17", "-Wall", n("native/check_core_selftest.cpp"), "-o", "{out}"]),
+        # the calibration, flip positions, unit lists, CU coverage and command line of the GPU checks, against the
+        # loops they replaced
+        (n(BIN, "check-core-selftest"), core_selftest,
+         ["g++", "-O2", "-std=c++17", "-Wall", core_selftest[0], "-o", "{out}"]),
         # hbm-check's region, chunks, offsets, seeds and self-test slots
         (n(BIN, "hbm-plan-selftest"), plan_selftest, ["g++", "-O2", "-std=c++17", "-Wall", plan_selftest[0], "-o", "{out}"]),
         # atomic-check's slot map and its inverse, operands, expected values and the bounds that keep them exact
@@ -132,8 +134,8 @@ def targets(sanitize=False, cpu_only=False):
             (n(BIN, "sysfs-prefetch-selftest-tsan"), [n("native/sysfs_prefetch_selftest.cpp"), n("native/sysfs_prefetch.h")],
              ["g++", "-O1", "-std=c++17", "-fsanitize=thread", "-fno-omit-frame-pointer", "-g",
               n("native/sysfs_prefetch_selftest.cpp"), "-pthread", "-ldl", "-o", "{out}"]),
-            (n(BIN, "check-core-selftest-asan"), [n("native/check_core_selftest.cpp"), n("kernels/check_core.h")],
-             ["g++", "-O1", "-std=c++17", *san, n("native/check_core_selftest.cpp"), "-o", "{out}"]),
+            (n(BIN, "check-core-selftest-asan"), core_selftest,
+             ["g++", "-O1", "-std=c++17", *san, core_selftest[0], "-o", "{out}"]),
             (n(BIN, "hbm-plan-selftest-asan"), plan_selftest,
              ["g++", "-O1", "-std=c++17", *san, plan_selftest[0], "-o", "{out}"]),
             (n(BIN, "atomic-plan-selftest-asan"), atomic_selftest,
@@ -163,13 +165,14 @@ def targets(sanitize=False, cpu_only=False):
         chk = [n("kernels/mfma_check.h"), *base]
         lp = [n("kernels/mfma_check_lp.h"), *chk]
         wide = [n("kernels/mfma_check_sparse.h"), n("kernels/mfma_check_wide.h"), *lp]
-        cu = [n("kernels/cu_check.h"), *base]
+        cli = n("kernels/check_cli.h")  # of the four check programs; _hipops takes no command line
+        cu = [n("kernels/cu_check.h"), n("kernels/cu_run.h"), *base]
         hbm = [n("kernels/hbm_check.h"), n("kernels/hbm_plan.h"), *base]
         xgmi = [n("kernels/xgmi_verify.h"), n("kernels/xgmi_pattern.h"), *base]
         atomic = [n("kernels/atomic_check.h"), n("kernels/atomic_plan.h"), *base]
-        lane = [n("kernels/lane_check.h"), n("kernels/lane_plan.h"), *base]
+        lane = [n("kernels/lane_check.h"), n("kernels/lane_plan.h"), n("kernels/cu_run.h"), *base]
         t += [
-            (n(OUT, "_hipops" + EXT), [n("native/hipops.hip"), n("kernels/cu_check.h"), *atomic[:2], *lane[:2], *hbm[:2], *xgmi[:2], *wide],
+            (n(OUT, "_hipops" + EXT), [n("native/hipops.hip"), *cu[:2], *atomic[:2], *lane[:2], *hbm[:2], *xgmi[:2], *wide],
              [*ho, "-shared", "-fPIC", *py, n("native/hipops.hip"), "-o", "{out}"]),
             (n(BIN, "rocm-vector-add"), [n("kernels/vector_add.hip"), *base], [*ho, n("kernels/vector_add.hip"), "-o", "{out}"]),
             # the HIP-free pod workload: a bare gfx950 code object, then the HSA host embedding it
@@ -182,12 +185,12 @@ def targets(sanitize=False, cpu_only=False):
               f'-I{ROCM}/include {n("kernels/hsa_vector_add.cpp")} -L{ROCM}/lib -Wl,-rpath,{ROCM}/lib -lhsa-runtime64 -pthread -ldl -o "$1"',
               hip, "{out}"]),
             (n(BIN, "hbm-probe"), [n("kernels/hbm_probe.hip"), *base], [*ho, n("kernels/hbm_probe.hip"), "-o", "{out}"]),
-            (n(BIN, "hbm-check"), [n("kernels/hbm_check.hip"), *hbm], [*ho, n("kernels/hbm_check.hip"), "-o", "{out}"]),
+            (n(BIN, "hbm-check"), [n("kernels/hbm_check.hip"), cli, *hbm], [*ho, n("kernels/hbm_check.hip"), "-o", "{out}"]),
             (n(BIN, "gpu-burn"), [n("kernels/gpu_burn.hip"), *chk], [*ho, n("kernels/gpu_burn.hip"), "-o", "{out}"]),
             (n(BIN, "mfma-check"), [n("kernels/mfma_check.hip"), *wide], [*ho, n("kernels/mfma_check.hip"), "-o", "{out}"]),
-            (n(BIN, "cu-check"), [n("kernels/cu_check.hip"), *cu], [*ho, n("kernels/cu_check.hip"), "-o", "{out}"]),
-            (n(BIN, "atomic-check"), [n("kernels/atomic_check.hip"), *atomic], [*ho, n("kernels/atomic_check.hip"), "-o", "{out}"]),
-            (n(BIN, "lane-check"), [n("kernels/lane_check.hip"), *lane], [*ho, n("kernels/lane_check.hip"), "-o", "{out}"]),
+            (n(BIN, "cu-check"), [n("kernels/cu_check.hip"), cli, *cu], [*ho, n("kernels/cu_check.hip"), "-o", "{out}"]),
+            (n(BIN, "atomic-check"), [n("kernels/atomic_check.hip"), cli, *atomic], [*ho, n("kernels/atomic_check.hip"), "-o", "{out}"]),
+            (n(BIN, "lane-check"), [n("kernels/lane_check.hip"), cli, *lane], [*ho, n("kernels/lane_check.hip"), "-o", "{out}"]),
             (n(BIN, "xgmi-probe"), [n("kernels/xgmi_probe.cpp"), *xgmi],
              [*ho, "-x", "hip", n("kernels/xgmi_probe.cpp"), *rocm_inc, *rpath, "-lrccl", "-o", "{out}"]),
         ]

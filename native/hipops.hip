@@ -50,20 +50,41 @@ static py::dict cu_location(const amdkube::CuLocation& l) {
   return d;
 }
 
-// the result of a per-CU check run (kernels/cu_check.h)
-static py::dict cu_check_result(const amdkube::CuCheckResult& r) {
-  py::dict o, by_unit;
-  py::list units, locations, bad, recs;
-  for (int u = 0; u < 3; ++u) {
-    if (r.units & (1 << u)) units.append(amdkube::CU_UNIT_NAMES[u]);
-    by_unit[amdkube::CU_UNIT_NAMES[u]] = r.errors_by_unit[u];
-  }
-  for (const amdkube::CuLocation& l : r.locations) locations.append(cu_location(l));
-  for (const amdkube::CuCheckBadCu& b : r.bad_cus) {
+static py::list bad_cu_list(const std::vector<amdkube::CuBadCu>& bad_cus) {
+  py::list bad;
+  for (const amdkube::CuBadCu& b : bad_cus) {
     py::dict d = cu_location(b.where);
     d["errors"] = b.errors;
     bad.append(d);
   }
+  return bad;
+}
+
+// the first fields of a check's result, those that do not depend on where it ran (kernels/cu_run.h)
+template <class Result>
+static py::dict cu_run_result(const Result& r, const char* const* names, int n) {
+  py::dict o, by_unit;
+  py::list units;
+  for (int u = 0; u < n; ++u) {
+    if (r.units & (1 << u)) units.append(names[u]);
+    by_unit[names[u]] = r.errors_by_unit[u];
+  }
+  o["ok"] = r.errors == 0;
+  o["errors"] = r.errors;
+  o["errors_by_unit"] = by_unit;
+  o["units"] = units;
+  o["rounds"] = r.rounds;
+  o["blocks"] = r.blocks;
+  o["launches"] = r.launches;
+  o["ms"] = r.ms;
+  return o;
+}
+
+// the result of a per-CU check run (kernels/cu_check.h)
+static py::dict cu_check_result(const amdkube::CuCheckResult& r) {
+  py::dict o = cu_run_result(r, amdkube::CU_UNIT_NAMES, 3);
+  py::list locations, recs;
+  for (const amdkube::CuLocation& l : r.locations) locations.append(cu_location(l));
   for (const amdkube::CuCheckRecord& e : r.first_errors) {
     py::dict d = cu_location(amdkube::cu_decode_location(e.hw_id, e.xcc_id));
     d["unit"] = amdkube::CU_UNIT_NAMES[e.unit < 3 ? e.unit : 0];
@@ -75,14 +96,6 @@ static py::dict cu_check_result(const amdkube::CuCheckResult& r) {
     d["want"] = e.want;
     recs.append(d);
   }
-  o["ok"] = r.errors == 0;
-  o["errors"] = r.errors;
-  o["errors_by_unit"] = by_unit;
-  o["units"] = units;
-  o["rounds"] = r.rounds;
-  o["blocks"] = r.blocks;
-  o["launches"] = r.launches;
-  o["ms"] = r.ms;
   o["lds_gbps"] = r.lds_gbps;
   o["valu_gops"] = r.valu_gops;
   o["cus"] = r.cus;
@@ -91,7 +104,7 @@ static py::dict cu_check_result(const amdkube::CuCheckResult& r) {
   o["locations"] = locations;
   // raw HW_ID and XCC_ID words of every workgroup of the timed launch
   o["block_loc"] = py::array_t<uint32_t>({static_cast<py::ssize_t>(r.blocks), static_cast<py::ssize_t>(2)}, r.block_loc.data());
-  o["bad_cus"] = bad;
+  o["bad_cus"] = bad_cu_list(r.bad_cus);
   o["first_errors"] = recs;
   return o;
 }
@@ -453,20 +466,11 @@ PYBIND11_MODULE(_hipops, m) {
       "lane_check",
       [](int rounds, double ms, int dev, uint32_t seed, int flips, int units) {
         const amdkube::LaneCheckResult r = nogil([&] { return amdkube::run_lane_check(rounds, ms, dev, seed, flips, units); });
-        py::dict o, by_unit;
-        py::list units_l, bad, recs;
-        for (int u = 0; u < 4; ++u) {
-          if (r.units & (1 << u)) units_l.append(amdkube::LANE_UNIT_NAMES[u]);
-          by_unit[amdkube::LANE_UNIT_NAMES[u]] = r.errors_by_unit[u];
-        }
-        for (const amdkube::LaneCheckBadCu& b : r.bad_cus) {
-          py::dict d = cu_location(b.where);
-          d["errors"] = b.errors;
-          bad.append(d);
-        }
+        py::dict o = cu_run_result(r, amdkube::LANE_UNIT_NAMES, 4);
+        py::list recs;
         for (const amdkube::LaneCheckRecord& e : r.first_errors) {
           py::dict d = cu_location(amdkube::cu_decode_location(e.hw_id, e.xcc_id));
-          d["simd"] = amdkube::lane_simd_of(e.hw_id);
+          d["simd"] = amdkube::cu_decode_simd(e.hw_id);
           d["unit"] = amdkube::LANE_UNIT_NAMES[e.unit < 4 ? e.unit : 0];
           d["block"] = e.block;
           d["round"] = e.round;
@@ -476,14 +480,6 @@ PYBIND11_MODULE(_hipops, m) {
           d["want"] = e.want;
           recs.append(d);
         }
-        o["ok"] = r.errors == 0;
-        o["errors"] = r.errors;
-        o["errors_by_unit"] = by_unit;
-        o["units"] = units_l;
-        o["rounds"] = r.rounds;
-        o["blocks"] = r.blocks;
-        o["launches"] = r.launches;
-        o["ms"] = r.ms;
         o["xlane_gops"] = r.xlane_gops;
         o["tr_gbps"] = r.tr_gbps;
         o["dma_gbps"] = r.dma_gbps;
@@ -495,7 +491,7 @@ PYBIND11_MODULE(_hipops, m) {
         // raw HW_ID of the 16 waves, then XCC_ID, of every workgroup of the timed launch
         o["block_loc"] = py::array_t<uint32_t>({static_cast<py::ssize_t>(r.blocks), static_cast<py::ssize_t>(amdkube::LANE_LOC_WORDS)},
                                                r.block_loc.data());
-        o["bad_cus"] = bad;
+        o["bad_cus"] = bad_cu_list(r.bad_cus);
         o["first_errors"] = recs;
         return o;
       },
